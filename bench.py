@@ -19,7 +19,11 @@ forcing interpolation -> forcing preparation with CALC_DECLIN's zenith angle -> 
 nothing: the grid is fixed, STRONG scaling).  `--dt 900` runs config 4 with STEPWTD = 2 (hdrv:247-248).
 
 `python bench.py --gpus N` without a torchrun environment starts the N ranks itself (children are started before anything
-touches the GPU).  Prints ONE JSON line on rank 0 (metric contract of the driver) with `roofline` and `cpu_baseline`.
+touches the GPU).  Prints ONE JSON line on rank 0 (metric contract of the driver) with `roofline`.  A plain run sets up, warms
+up, times `--steps` steps and reports them; `--full` adds the legs that take runs of their own: `cpu_baseline`, the N = 1
+reference legs (`scaling_reference`, `config2_reference`, `config5_reference`, `config5_smooth_reference`, `options_reference`,
+`host_path_reference`) and, for N > 1, `n1_reference` / `strong_scaling_efficiency`.  `--dump-outputs DIR` writes what the
+timed path computed in its last step (dump_outputs).
 """
 import argparse
 import json
@@ -829,6 +833,42 @@ def valu_roofline(pm, dv, dom_ms, source):
     return out
 
 
+DUMP_COLUMNS = 65536        # columns --dump-outputs samples from a larger tile: ~125 output words each, ~33 MB in all
+
+
+def dump_outputs(run, out_dir, suffix=""):
+    """--dump-outputs: the INOUT / OUT arrays of noahmplsm (and with OPT_RUN = 5 WTABLE_mmf_noahmp's own outputs) as the timed path
+    left them after its last step, as the caller receives them: tile order, without the ring.  A tile of more than DUMP_COLUMNS
+    columns is sampled at a fixed, seeded set of them (sorted tile-order indices, the same for every run of the same grid).  One
+    DIR/<name><suffix>.npy per array: float32, integer arrays as float64; shape (columns,) or (levels, columns)."""
+    import numpy as np
+    import torch
+    from noahmp_amd.abi import FIELD_INFO
+    run.ts.synchronize()
+    d, g = run.d, run.geom
+    nti, ntj = g["ite"] - g["its"] + 1, g["jte"] - g["jts"] + 1
+    n = nti * ntj
+    cols = np.arange(n) if n <= DUMP_COLUMNS else np.sort(np.random.Generator(np.random.Philox(20240)).choice(n, DUMP_COLUMNS, replace=False))
+    if (d.ni, d.nj) != (nti, ntj):               # the store is the memory block (tile + ring) in (i,j) order
+        cols = (cols // nti + g["jts"] - g["jms"]) * d.ni + cols % nti + g["its"] - g["ims"]
+    idx = torch.from_numpy(cols.astype(np.int64)).to(d.device)
+    perm = getattr(run, "perm", None) if run.sorted else None
+    if perm is not None:                         # tile position -> sorted position
+        p = perm.long()
+        inv = torch.empty_like(p)
+        inv[p] = torch.arange(p.numel(), device=p.device)
+        idx = inv[idx]
+    names = [k for k in d.a if k in FIELD_INFO and FIELD_INFO[k][2] != "in" and k != "dzs"]
+    if run.lateral:
+        names += [k for k in GW_ONLY_OUT if k in d.a]
+    os.makedirs(out_dir, exist_ok=True)
+    for k in names:
+        v = d.a[k]
+        v = v.permute(1, 0, 2).reshape(v.shape[1], -1)[:, idx] if v.dim() == 3 else v.reshape(-1)[idx]
+        v = v.cpu().numpy()
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), v if v.dtype == np.float32 else v.astype(np.float64))
+
+
 def timed_leg(run, steps, warmup, barrier):
     """warm-up, then `steps` timed steps between two barriers; -> seconds of the timed region"""
     it = 0
@@ -1100,6 +1140,13 @@ def main():
                     help="N > 1: skip rank 0's own run of the same workload on the whole grid (n1_reference / strong_scaling_efficiency)")
     ap.add_argument("--no-scaling-reference", action="store_true",
                     help="N = 1, default workload: skip the short config-4 run that gives the N = 1 point of the --gpus N curve")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, each leg timed on its own: the CPU baseline, the N = 1 reference "
+                         "legs (config 4, config 2, config 5, other option sets, the host-array path) and, for N > 1, rank 0's run of the "
+                         "whole grid (n1_reference); the --no-* options above skip single legs of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the arrays the timed path computed in its last step to DIR/<name>.npy (float32 / "
+                         "float64, tile order; a fixed, seeded sample of %d columns of a larger tile; N > 1: DIR/<name>.rank<r>.npy)" % DUMP_COLUMNS)
     ap.add_argument("--dump", default=None, help="write every rank's tile (tile order, without the ring) to DUMP.rank<r>.npz after the run")
     ap.add_argument("--cpu-baseline-only", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -1149,7 +1196,7 @@ def main():
     # strong_scaling_efficiency = value / (N x n1_reference.value) and needs no second run to be read.  (The default N = 1 run is the
     # headline workload, config 3; the default N > 1 workload is config 4, ~13 % more work per column.)
     n1_ref = None
-    if world > 1 and not args.no_n1_reference:
+    if world > 1 and args.full and not args.no_n1_reference:
         if rank == 0:
             t1 = time.perf_counter()
             solo = Comm.solo(dev_index)
@@ -1199,6 +1246,8 @@ def main():
     kernel_ms_max = comm.reduce_max(run.kernel_ms)
     kernel_ms_min = comm.reduce_min(run.kernel_ms)
 
+    if args.dump_outputs:
+        dump_outputs(run, args.dump_outputs, "" if world == 1 else ".rank%d" % rank)
     if args.dump:
         run.dump(args.dump + ".rank%d.npz" % rank)
     if rank == 0 and os.environ.get("NMP_PHASE_PROF"):
@@ -1230,7 +1279,7 @@ def main():
     # N = 1, 2, 4, 8 has its N = 1 point on the SAME workload, the default N = 1 run measures it too, after the headline (a second,
     # separately timed region of the same length; reported beside the headline, never as `value`).
     scaling_ref = config2_ref = config5_ref = config5_smooth_ref = options_ref = host_ref = None
-    if world == 1 and workload == "config3" and args.workload is None and not args.no_scaling_reference:
+    if world == 1 and workload == "config3" and args.workload is None and args.full and not args.no_scaling_reference:
         summary = dict(tsk_bin=run.tsk_bin, class_ms=list(run.class_ms), n_land=run.n_land, n_adv=run.n_adv, resorts=run.resorts, stale=list(run.stale_seen),
                        sorted=run.sorted, lateral=run.lateral, tile_cells=run.tile_cells, stepwtd=run.stepwtd, kernel_ms=run.kernel_ms,
                        hour_ms=dict(run.hour_ms), hour_ms_warm=dict(getattr(run, "hour_ms_warm", {})), step_hours=list(run.step_hours))
@@ -1300,7 +1349,7 @@ def main():
         run.hour_ms, run.hour_ms_warm, run.step_hours = summary["hour_ms"], summary["hour_ms_warm"], summary["step_hours"]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # CPU leg: after the timed GPU region, in a child process that never initialises the GPU
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", workload], capture_output=True, text=True)
         for line in r.stdout.splitlines():

@@ -11,9 +11,9 @@ from noahmp_amd.abi import StepArgs, Tables, WtableArgs, tables_to_dict
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 REF_DIR = os.path.join(_HERE, "_ref")
-# table text files: read from the reference tree in the dev container; on the GPU box the
-# reference library is used with tables injected from the committed fixture instead.
-REF_RUN_DIR = "/root/reference/run"
+# the reference's parameter table files (VEGPARM / SOILPARM / GENPARM / MPTABLE.TBL, data only), committed as test fixtures: its
+# table readers and NOAHMP_INIT open them from the current directory
+REF_RUN_DIR = os.path.join(os.path.dirname(_HERE), "tests", "golden", "tables")
 
 
 def available(opt="O0"):

@@ -5,7 +5,8 @@ Writes small compressed fixtures (data only) next to this script:
   golden_config1.npz    BASELINE config 1: single column, 24 hourly steps, every output each step
   golden_mixed.npz      64x4 mixed tile (snow 0..3 layers, urban, barren, 9 veg types): initial
                         state + full state after steps 1, 12, 24 of a free run
-  golden_opts.npz       same tile, one step at hour 12, for each entry of the OPT_* sweep
+  golden_opts.npz       same tile, one step at hour 12, for each entry of the OPT_* sweep (stored as golden_opts_part<k>.npz:
+                        npz_parts.py)
 Usage:  python tests/golden/make_golden.py
 """
 import os
@@ -19,6 +20,10 @@ from noahmp_amd import synth  # noqa: E402
 from noahmp_amd.state import ModelConfig  # noqa: E402
 from noahmp_amd.tables import load_tables  # noqa: E402
 from oracle.reflib import RefLib  # noqa: E402
+try:
+    from golden import npz_parts  # noqa: E402  (imported from tests/)
+except ImportError:
+    import npz_parts  # noqa: E402  (run as a script: next to it)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SWEEP = [dict(), dict(idveg=1), dict(idveg=2), dict(idveg=4), dict(idveg=5), dict(iopt_crs=2),
@@ -83,8 +88,8 @@ def main():
             if FIELD_INFO[k][2] != "in":
                 out["opt%02d/%s" % (n, k)] = v.copy()
     out["sweep"] = np.array([repr(k) for k in SWEEP])
-    np.savez_compressed(os.path.join(HERE, "golden_opts.npz"), **out)
-    for f in ("golden_config1.npz", "golden_mixed.npz", "golden_opts.npz"):
+    opts = npz_parts.save(os.path.join(HERE, "golden_opts.npz"), out)
+    for f in ["golden_config1.npz", "golden_mixed.npz"] + [os.path.basename(p) for p in opts]:
         print(f, os.path.getsize(os.path.join(HERE, f)) // 1024, "KiB")
 
 

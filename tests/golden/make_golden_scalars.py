@@ -1,4 +1,4 @@
-"""Write tests/golden/golden_scalars.npz by RUNNING THE COMPILED REFERENCE (oracle/_ref, -O0 float32): the sweep over the scalars
+"""Write tests/golden/golden_scalars.npz (as golden_scalars_part<k>.npz: npz_parts.py) by RUNNING THE COMPILED REFERENCE (oracle/_ref, -O0 float32): the sweep over the scalars
 that are uniform over the grid at the noahmplsm boundary (drv:51-83) -- DT (NITER doubling lsm:7850-7857, FACT, the accumulators,
 COMPACT, PHASECHANGE), DZS (ZSOIL drv:392-395: root fractions, the tridiagonal coefficients, ZWTEQ), YR (YEARLEN drv:381-390),
 JULIAN on both hemispheres (lsm:1054-1071), DZ8W (the forcing height).  One cold start by the reference's NOAHMP_INIT per case,
@@ -15,6 +15,10 @@ from noahmp_amd import synth  # noqa: E402
 from noahmp_amd.state import ModelConfig  # noqa: E402
 from noahmp_amd.tables import load_tables  # noqa: E402
 from oracle.reflib import RefLib  # noqa: E402
+try:
+    from golden import npz_parts  # noqa: E402  (imported from tests/)
+except ImportError:
+    import npz_parts  # noqa: E402  (run as a script: next to it)
 
 DZS2 = (0.05, 0.25, 0.7, 1.5)
 # name -> cfg overrides, YR, JULIAN at the first step, steps, local hour of the first step, rain [mm/h] in hours 10-12, snapshots
@@ -87,8 +91,8 @@ def main():
         print("%-14s %2d steps, ISNOW states %s, SMOIS(1) %.3f..%.3f" % (name, c["nsteps"], sorted(seen),
               s.a["smois"][:, 0, :].min(), s.a["smois"][:, 0, :].max()))
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden_scalars.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes")
+    for p in npz_parts.save(path, out):
+        print("wrote", p, os.path.getsize(p), "bytes")
 
 
 if __name__ == "__main__":

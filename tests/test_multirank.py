@@ -122,7 +122,11 @@ def test_auto_mover_is_agreed_on_by_all_ranks(fail_rank):
     """`halo="auto"`: every rank starts the engine's own mover and runs the checked probe exchange (here with the socket transport on
     host planes, so that it runs without a GPU); it is used only if EVERY rank succeeded -- one failing rank sends all of them to the
     torch.distributed mover together -- and either way the ring arrives (4 ranks = 2 x 2: every rank has a diagonal neighbour)."""
+    import torch
     world = 4
+    ngpu = torch.cuda.device_count()
+    if 0 < ngpu < world:            # the engine's mover binds rank r to GPU r
+        pytest.skip("needs %d GPUs or none, found %d" % (world, ngpu))
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     p = _free_port()
@@ -381,6 +385,29 @@ def test_bench_two_ranks_equal_one_rank(workload, tmp_path, monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("workload,grid", [("config3", (96, 130)), ("config4", (96, 130)), ("config3", (320, 216))])
+def test_bench_dump_outputs_are_the_last_step_in_tile_order(workload, grid, tmp_path):
+    """`bench.py --dump-outputs DIR`: every INOUT / OUT array of the last timed step (with OPT_RUN = 5 also WTABLE_mmf_noahmp's own
+    outputs) as float32 / float64 .npy in tile order, equal to the whole-tile dump of the same run -- all columns of a small tile, the
+    fixed seeded sample of 65536 columns of a larger one (320 x 216)."""
+    out = os.path.join(str(tmp_path), "outputs")
+    res, dump = _run_bench(["--gpus", "1", "--workload", workload, "--ni", str(grid[0]), "--nj", str(grid[1]), "--dump-outputs", out],
+                           str(tmp_path), "whole")
+    assert res["steps"] == 5 and res["ms_per_step"] > 0
+    whole = np.load(dump + ".rank0.npz")
+    n = grid[0] * grid[1]
+    cols = np.arange(n) if n <= 65536 else np.sort(np.random.Generator(np.random.Philox(20240)).choice(n, 65536, replace=False))
+    names = sorted(f[:-len(".npy")] for f in os.listdir(out))
+    assert names == sorted(k for k in whole.files if k != "geom")
+    for k in names:
+        v = np.load(os.path.join(out, k + ".npy"))
+        w = whole[k]
+        w = w.transpose(1, 0, 2).reshape(w.shape[1], -1)[:, cols] if w.ndim == 3 else w.reshape(-1)[cols]
+        assert v.dtype == (np.float32 if w.dtype == np.float32 else np.float64) and v.shape == w.shape, k
+        assert np.array_equal(v, w.astype(v.dtype), equal_nan=True), k
+
+
+@pytest.mark.gpu
 def test_bench_ranks_agree_when_rccl_refuses(tmp_path, tmp_path_factory):
     """`bench.py --gpus 2` with the default backend (nccl = RCCL) on a box whose ranks share one GPU: RCCL refuses a communicator
     with a duplicate device on every rank; the ranks learn of it over the gloo control plane, switch TOGETHER to host-staged edges
@@ -433,7 +460,7 @@ def test_bench_north_star_tiling_equals_one_rank(world, workload, halo, tmp_path
         whole = np.load(d1 + ".rank0.npz")
     else:
         whole = _one_rank_dump(workload, tmp_path_factory)
-    res, dn = _run_bench(["--gpus", str(world)] + common + (["--halo", halo] if workload == "config4" else []), str(tmp_path), "many")
+    res, dn = _run_bench(["--gpus", str(world), "--full"] + common + (["--halo", halo] if workload == "config4" else []), str(tmp_path), "many")
     assert res["n_gpus"] == world and res["scaling"] == "strong"
     # the N > 1 line is self-contained: the N = 1 point of the SAME workload (rank 0, whole grid, same steps) and the efficiency against it
     n1 = res["n1_reference"]

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_store
+from golden import npz_parts
 from noahmp_amd import synth
 from noahmp_amd.abi import FIELD_INFO
 from noahmp_amd.state import ModelConfig
@@ -47,7 +48,7 @@ def test_port_matches_golden_mixed(port):
 
 def test_port_matches_golden_option_sweep(port):
     """One step at noon for every OPT_* alternative (22 option sets): bit-exact."""
-    g = np.load(os.path.join(GOLDEN, "golden_opts.npz"))
+    g = npz_parts.load(os.path.join(GOLDEN, "golden_opts.npz"))
     sweep = [eval(x) for x in g["sweep"]]
     base = load_store(g, "init", 32, 4)
     for n, kw in enumerate(sweep):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_store
+from golden import npz_parts
 from noahmp_amd import synth
 from noahmp_amd.abi import FIELD_INFO
 from noahmp_amd.state import ModelConfig
@@ -105,7 +106,7 @@ def test_mixed_tile_free_run_vs_golden(engine):
 
 def test_option_sweep_vs_golden(engine):
     """Every OPT_* alternative (22 option sets), one step at noon, vs the reference."""
-    g = np.load(os.path.join(GOLDEN, "golden_opts.npz"))
+    g = npz_parts.load(os.path.join(GOLDEN, "golden_opts.npz"))
     sweep = [eval(x) for x in g["sweep"]]
     base = load_store(g, "init", 32, 4)
     for n, kw in enumerate(sweep):

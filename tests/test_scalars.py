@@ -14,6 +14,7 @@ import pytest
 
 from conftest import GOLDEN, load_store
 from noahmp_amd import synth
+from golden import npz_parts
 from golden.make_golden_scalars import CASES, case_config, case_forcing
 from test_matrix import _same
 
@@ -23,7 +24,7 @@ FORCING = ("coszin", "swdown", "glw", "t3d", "rainbl", "qv3d", "u_phy", "v_phy",
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(FIX)
+    return npz_parts.load(FIX)
 
 
 def _drive(g, name, init, step, snapshot):
