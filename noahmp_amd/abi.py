@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libnoahmp_hip.so")
 
 MEM_HOST, MEM_DEVICE = 0, 1
 SORT_VEG, SORT_SNOW, SORT_SNOW_FIRST, SORT_TAIR, SORT_COST = 1, 2, 4, 8, 16
-HALO_TCP, HALO_RCCL = 0, 1
+HALO_TCP, HALO_RCCL, HALO_IPC = 0, 1, 2
 
 
 def _step_ctype(kind):

@@ -11,7 +11,10 @@
 //   * transport NOAHMP_HALO_RCCL: ncclSend / ncclRecv of the packed edges to / from all <= 8 neighbours in ONE group on the caller's
 //     stream (RCCL over xGMI, GPU-direct; librccl is loaded with dlopen at init, its unique id travels over the rendezvous);
 //   * transport NOAHMP_HALO_TCP: the packed edges travel over the rendezvous sockets (host planes directly, device planes through a
-//     pinned staging buffer) -- the form the CPU tests and single-GPU checks use, and a fallback where RCCL is not available.
+//     pinned staging buffer) -- the form the CPU tests and single-GPU checks use, and a fallback where RCCL is not available;
+//   * transport NOAHMP_HALO_IPC: every rank packs its edges into a device buffer of its own that it exports with a HIP IPC memory
+//     handle; the sockets carry small control tokens only, and ONE kernel per call (halo_ipc_pull_kernel) reads the neighbours'
+//     messages straight from their mapped buffers into the ring cells (ranks that share a GPU, or peers over xGMI).
 // All planes of a call share the messages.
 #include <arpa/inet.h>
 #include <dlfcn.h>
@@ -64,6 +67,17 @@ struct Halo {
   // staging
   uint32_t* d_send = nullptr; uint32_t* d_recv = nullptr; size_t d_words = 0;
   uint32_t* h_send = nullptr; uint32_t* h_recv = nullptr; size_t h_words = 0; bool h_pinned = false;
+  // IPC transport: the exported buffer (two halves of `cap` words, call parity), the allocations it outgrew (alive until finalize:
+  // a neighbour may still map them), the neighbours' mapped buffers, and the events of the last pack and pull
+  bool ipc_live = false;                      // init succeeded: finalize runs the close / bye / free sequence
+  uint32_t* ipc_buf = nullptr; long ipc_cap = 0; int ipc_gen = 0; hipIpcMemHandle_t ipc_handle;
+  std::vector<uint32_t*> ipc_retired;
+  long long ipc_seq = 0;
+  int sent_gen[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  void* peer_ptr[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int peer_gen[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long peer_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  hipEvent_t ev_pack = nullptr, ev_pull = nullptr; bool pull_pending = false;
 } H;
 
 int fail(const std::string& m, int rc = -109) { g.last_error = "noahmp_hip_halo: " + m; return rc; }
@@ -193,6 +207,23 @@ __global__ void __launch_bounds__(256) halo_pack_kernel(const PackArgs k, uint32
   else *slot = plane[e.first + (long)q * e.stride];
 }
 
+// IPC transport: the ring cells of all planes of a call straight from the neighbours' exported buffers, one launch.  k.e[ed] describes
+// the ring cells on side ed (as the unpack pass of halo_pack_kernel), src[ed] the neighbour's message for this rank (plane-major,
+// k.e[ed].count words per plane); every src[ed] + n * count was checked against the neighbour's buffer on the host before the launch.
+struct PullArgs { PackArgs k; const uint32_t* src[kMaxEdges]; };
+__global__ void __launch_bounds__(256) halo_ipc_pull_kernel(const PullArgs a) {
+  const PackArgs& k = a.k;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= k.start[k.nedge]) return;
+  int ed = 0;
+  while (ed + 1 < k.nedge && t >= k.start[ed + 1]) ed++;               // <= 8 edges
+  const EdgeDesc& e = k.e[ed];
+  const long r = t - k.start[ed];
+  const int q = (int)(r % e.count), p = (int)(r / e.count);
+  uint32_t* plane = (uint32_t*)k.planes[p];
+  plane[e.first + (long)q * e.stride] = a.src[ed][(long)p * e.count + q];
+}
+
 void host_pack(const PackArgs& k, uint32_t* buf, int unpack) {
   for (int ed = 0; ed < k.nedge; ed++)
     for (int p = 0; p < k.n; p++) {
@@ -229,6 +260,128 @@ int ensure_staging(size_t words, bool device) {
   return 0;
 }
 
+// ---- IPC transport.  One control token per link and call; the 64-byte memory handle follows it when `generation` changed.
+struct IpcToken { long long seq; int n, generation; long long cap; int parity, pad; long long offset_words, count_words; };
+static_assert(sizeof(hipIpcMemHandle_t) == 64 && sizeof(IpcToken) == 48, "fixed-size control messages");
+constexpr long long kByeSeq = -1;             // finalize: "this rank has closed every mapping of its neighbours' buffers"
+
+// the exported buffer holds at least `words` words per half; growing exports a new allocation (generation + 1) and keeps the old one
+int ipc_ensure(long words) {
+  if (H.ipc_buf && words <= H.ipc_cap) return 0;
+  const long cap = words > 2 * H.ipc_cap ? words : 2 * H.ipc_cap;
+  uint32_t* b = nullptr;
+  HIPCHK(hipMalloc((void**)&b, (size_t)cap * 2 * 4));
+  hipIpcMemHandle_t h;
+  const hipError_t e = hipIpcGetMemHandle(&h, b);
+  if (e != hipSuccess) { hipFree(b); return fail(std::string("hipIpcGetMemHandle: ") + hipGetErrorString(e), -100); }
+  if (H.ipc_buf) H.ipc_retired.push_back(H.ipc_buf);
+  H.ipc_buf = b; H.ipc_cap = cap; H.ipc_handle = h; H.ipc_gen++;
+  return 0;
+}
+
+// Per call: (1) the previous pull has completed; (2) pack into half seq & 1, wait for it; (3) tokens to / from every neighbour in the
+// socket transport's link order; (4) every token checked on the host; (5) mappings of new generations opened; (6) ONE pull launch.
+// Nothing here waits on the device for another process: the only cross-process waits are the blocking socket transfers.
+int exchange_ipc(int n, const PackArgs& pk, const PackArgs& up, const int* slot_of, long words, hipStream_t s) {
+  if (!H.ev_pack) HIPCHK(hipEventCreateWithFlags(&H.ev_pack, hipEventDisableTiming));
+  if (!H.ev_pull) HIPCHK(hipEventCreateWithFlags(&H.ev_pull, hipEventDisableTiming));
+  if (H.pull_pending) { HIPCHK(hipEventSynchronize(H.ev_pull)); H.pull_pending = false; }
+  int rc = ipc_ensure(words);
+  if (rc) return rc;
+  const long long seq = ++H.ipc_seq;
+  const int parity = (int)(seq & 1);
+  const unsigned nblk = (unsigned)((words + 255) / 256);
+  hipLaunchKernelGGL(halo_pack_kernel, dim3(nblk), dim3(256), 0, s, pk, H.ipc_buf + (long)parity * H.ipc_cap, 0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(H.ev_pack, s));
+  HIPCHK(hipEventSynchronize(H.ev_pack));
+  IpcToken in[kMaxEdges];
+  hipIpcMemHandle_t in_h[kMaxEdges];
+  bool in_new[kMaxEdges];
+  for (int i = 0; i < pk.nedge; i++) {              // links in their global order, on a link the lower rank sends first (as the socket transport)
+    const int d = slot_of[i], peer = H.nb[d], fd = H.sock[d];
+    IpcToken out; memset(&out, 0, sizeof out);
+    out.seq = seq; out.n = n; out.generation = H.ipc_gen; out.cap = H.ipc_cap; out.parity = parity;
+    out.offset_words = pk.e[i].buf_off; out.count_words = (long long)n * pk.e[i].count;
+    const bool out_new = H.sent_gen[d] != H.ipc_gen;
+    errno = 0;
+    bool ok = true;
+    auto send_tok = [&] { return send_all(fd, &out, sizeof out) && (!out_new || send_all(fd, &H.ipc_handle, sizeof H.ipc_handle)); };
+    auto recv_tok = [&] {
+      if (!recv_all(fd, &in[i], sizeof in[i])) return false;
+      in_new[i] = in[i].seq > 0 && in[i].generation != H.peer_gen[d];
+      return !in_new[i] || recv_all(fd, &in_h[i], sizeof in_h[i]);
+    };
+    if (H.rank < peer) ok = send_tok() && recv_tok();
+    else ok = recv_tok() && send_tok();
+    if (!ok) return fail(std::string((errno == EAGAIN || errno == EWOULDBLOCK) ? "timeout (NMP_HALO_IO_TIMEOUT_S) in the" : "failed") +
+                         " token transfer with rank " + std::to_string(peer));
+    H.sent_gen[d] = H.ipc_gen;
+  }
+  // every token checked before anything is opened or launched: a bad offset never reaches a kernel
+  for (int i = 0; i < pk.nedge; i++) {
+    const int d = slot_of[i], peer = H.nb[d];
+    const IpcToken& t = in[i];
+    const std::string who = " from rank " + std::to_string(peer);
+    if (t.seq != seq || t.n != n)
+      return fail("call " + std::to_string(t.seq) + " with " + std::to_string(t.n) + " planes" + who + ", this rank is in call " +
+                  std::to_string(seq) + " with " + std::to_string(n) + " (the ranks' calls are out of step)", -104);
+    if (t.count_words != (long long)n * up.e[i].count)
+      return fail("message of " + std::to_string(t.count_words) + " words" + who + " for a ring side of " + std::to_string(up.e[i].count) +
+                  " cells x " + std::to_string(n) + " planes (the tiles do not fit together)", -105);
+    const long cap = in_new[i] ? (long)t.cap : H.peer_cap[d];
+    if (t.generation < 1 || (!in_new[i] && t.cap != cap) || cap < 1 || t.parity != parity || t.offset_words < 0 || t.count_words < 1 ||
+        t.count_words > cap || t.offset_words > cap - t.count_words)
+      return fail("token" + who + " outside its buffer (generation " + std::to_string(t.generation) + ", cap " + std::to_string(t.cap) +
+                  ", parity " + std::to_string(t.parity) + ", offset " + std::to_string(t.offset_words) + ", count " +
+                  std::to_string(t.count_words) + ")", -106);
+  }
+  PullArgs pa;
+  pa.k = up;
+  for (int i = 0; i < pk.nedge; i++) {
+    const int d = slot_of[i];
+    if (in_new[i]) {                               // one open per (peer, generation); the previous mapping is no longer read (step 1)
+      if (H.peer_ptr[d]) { hipIpcCloseMemHandle(H.peer_ptr[d]); H.peer_ptr[d] = nullptr; H.peer_gen[d] = 0; }
+      void* p = nullptr;
+      const hipError_t e = hipIpcOpenMemHandle(&p, in_h[i], hipIpcMemLazyEnablePeerAccess);
+      if (e != hipSuccess) return fail("hipIpcOpenMemHandle (rank " + std::to_string(H.nb[d]) + "): " + hipGetErrorString(e), -100);
+      H.peer_ptr[d] = p; H.peer_gen[d] = in[i].generation; H.peer_cap[d] = (long)in[i].cap;
+    }
+    pa.src[i] = (const uint32_t*)H.peer_ptr[d] + (long)parity * H.peer_cap[d] + in[i].offset_words;
+  }
+  hipLaunchKernelGGL(halo_ipc_pull_kernel, dim3(nblk), dim3(256), 0, s, pa);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(H.ev_pull, s));
+  H.pull_pending = true;
+  return 0;
+}
+
+// finalize of the IPC transport: no exporter frees before its importers have closed their mappings
+void ipc_finalize() {
+  if (H.pull_pending && H.ev_pull) hipEventSynchronize(H.ev_pull);
+  for (int d = 0; d < 8; d++) if (H.peer_ptr[d]) { hipIpcCloseMemHandle(H.peer_ptr[d]); H.peer_ptr[d] = nullptr; }
+  bool all_bye = true;
+  if (H.ipc_live) {
+    IpcToken bye; memset(&bye, 0, sizeof bye); bye.seq = kByeSeq;
+    for (int d = 0; d < 8; d++) if (H.sock[d] >= 0 && !send_all(H.sock[d], &bye, sizeof bye)) all_bye = false;
+    const double deadline = now_s() + halo_timeout_s();
+    for (int d = 0; d < 8; d++) {
+      if (H.sock[d] < 0) continue;
+      const double left = deadline - now_s();
+      IpcToken t;
+      if (left <= 0.0) { all_bye = false; break; }
+      set_io_timeout(H.sock[d], left);
+      if (!recv_all(H.sock[d], &t, sizeof t) || t.seq != kByeSeq) all_bye = false;
+    }
+  }
+  if (all_bye) {                                   // else leak them: a neighbour may still map them; process exit reclaims them
+    if (H.ipc_buf) hipFree(H.ipc_buf);
+    for (uint32_t* b : H.ipc_retired) hipFree(b);
+  }
+  if (H.ev_pack) hipEventDestroy(H.ev_pack);
+  if (H.ev_pull) hipEventDestroy(H.ev_pull);
+}
+
 // the one phase: send[d] goes to neighbour slot d, recv[d] comes from it (absent neighbours are skipped)
 int exchange_all(int n, void* const* planes, bool device, hipStream_t s, const EdgeDesc* send, const EdgeDesc* recv) {
   PackArgs pk; memset(&pk, 0, sizeof pk);
@@ -249,6 +402,7 @@ int exchange_all(int n, void* const* planes, bool device, hipStream_t s, const E
   }
   if (!pk.nedge) return 0;
   pk.start[pk.nedge] = up.start[up.nedge] = words;
+  if (H.transport == NOAHMP_HALO_IPC) return exchange_ipc(n, pk, up, slot_of, words, s);
   int rc = ensure_staging((size_t)words, device);
   if (rc) return rc;
   const unsigned nblk = (unsigned)((words + 255) / 256);
@@ -309,7 +463,7 @@ static int init_failed(const std::string& m, int rc = -109) {
 int noahmp_hip_halo_init(int rank, int nranks, const char* master_addr, int master_port, int transport) {
   if (H.up) noahmp_hip_halo_finalize();
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail("bad rank / nranks");
-  if (transport != NOAHMP_HALO_TCP && transport != NOAHMP_HALO_RCCL) return fail("unknown transport");
+  if (transport != NOAHMP_HALO_TCP && transport != NOAHMP_HALO_RCCL && transport != NOAHMP_HALO_IPC) return fail("unknown transport");
   H.rank = rank; H.nranks = nranks; H.transport = transport;
   nprocs_xy(nranks, H.npx, H.npy);
   const int ipx = rank % H.npx, ipy = rank / H.npx;                               // rank = iprocy*nprocx + iprocx (mpp:93-107)
@@ -325,7 +479,8 @@ int noahmp_hip_halo_init(int rank, int nranks, const char* master_addr, int mast
   const double timeout = halo_timeout_s(), deadline = now_s() + timeout;
   FdSet tmp;
   // ---- rendezvous: every rank opens a listener; rank 0 collects (ip, port, status) of all and hands the table out.  A rank that cannot
-  // take part (no librccl for the RCCL transport) says so in its hello, and rank 0 tells everybody: all ranks fail together, none waits.
+  // take part (no librccl for the RCCL transport, no HIP device for the IPC one) says so in its hello, and rank 0 tells everybody: all
+  // ranks fail together, none waits.
   int my_port = 0;
   const int lfd = tmp.add(listen_on(0, &my_port));
   if (lfd < 0) return init_failed("cannot open a listening socket");
@@ -336,6 +491,9 @@ int noahmp_hip_halo_init(int rank, int nranks, const char* master_addr, int mast
   if (transport == NOAHMP_HALO_RCCL) {
     if (load_rccl()) { my_abort = 1; my_reason = g.last_error; }
     else if (rank == 0 && H.rccl.GetUniqueId(&uid)) { my_abort = 1; my_reason = "ncclGetUniqueId failed"; }
+  }
+  if (transport == NOAHMP_HALO_IPC) {               // on the rank's current device; buffers come with the first exchange (tile geometry)
+    if (nmp_host::ensure_init()) { my_abort = 1; my_reason = "the IPC transport needs a HIP device on every rank: " + g.last_error; }
   }
   int abort_all = my_abort;
   if (rank == 0) {
@@ -396,6 +554,7 @@ int noahmp_hip_halo_init(int rank, int nranks, const char* master_addr, int mast
     const int e = H.rccl.CommInitRank(&H.comm, nranks, uid, rank);
     if (e) return init_failed(std::string("ncclCommInitRank: ") + (H.rccl.GetErrorString ? H.rccl.GetErrorString(e) : "error"));
   }
+  H.ipc_live = transport == NOAHMP_HALO_IPC;
   return 0;
 }
 
@@ -410,6 +569,7 @@ int noahmp_hip_exchange_halo(int n, void* const* planes, const int32_t* index8, 
   if ((H.nb[0] >= 0 && i0 < 1) || (H.nb[1] >= 0 && ite + 1 > ime) || (H.nb[2] >= 0 && j0 < 1) || (H.nb[3] >= 0 && jte + 1 > jme))
     return fail("the memory block (ims:ime, jms:jme) does not hold the 1-cell ring towards every neighbour", -103);
   const bool device = mem == NOAHMP_MEM_DEVICE;
+  if (H.transport == NOAHMP_HALO_IPC && !device) return fail("the IPC transport exchanges device-resident planes");   // -109, as RCCL
   hipStream_t s = nullptr;
   if (device) {
     int rc = nmp_host::ensure_init();
@@ -466,6 +626,7 @@ int noahmp_hip_halo_selftest_rccl(int words) {
 }
 
 int noahmp_hip_halo_finalize(void) {
+  if (H.transport == NOAHMP_HALO_IPC) ipc_finalize();        // before the sockets close: they carry the bye tokens
   for (int d = 0; d < 8; d++) { if (H.sock[d] >= 0) close(H.sock[d]); H.sock[d] = -1; }
   if (H.comm && H.rccl.CommDestroy) H.rccl.CommDestroy(H.comm);
   H.comm = nullptr;

@@ -9,8 +9,9 @@ node, and every decision about the device transports below is agreed over it BEF
 alone to leave a process group strands the others in it).  The DATA plane for device tensors is RCCL ("nccl" on ROCm, xGMI inside a
 node), brought up second and tested with one all-reduce; when any rank fails, all ranks run the ring over gloo (host-staged edges).
 
-Ring movers (``halo``): "rccl" / "tcp" -- the engine's own C-ABI exchange noahmp_hip_exchange_halo (noahmp_halo.hip; what a
-Fortran / MPI caller binds) with its RCCL or socket transport; "torch" -- torch.distributed
+Ring movers (``halo``): "rccl" / "tcp" / "ipc" -- the engine's own C-ABI exchange noahmp_hip_exchange_halo (noahmp_halo.hip; what
+a Fortran / MPI caller binds) with its RCCL, socket or HIP-IPC transport (ipc: device planes only, the
+neighbours' buffers read on the device; only by explicit request); "torch" -- torch.distributed
 batch_isend_irecv (RCCL send/recv for device planes under nccl, host-staged under gloo); "auto" (default) -- the C-ABI RCCL mover
 when RCCL is up and its start + a checked probe exchange succeed on EVERY rank within a time limit, else "torch".
 All movers fill the ring in ONE phase: the four tile edges and the four corner cells travel to the eight neighbours at once --
@@ -106,7 +107,7 @@ class Comm:
             else:
                 self.backend, self.dev_group = "nccl", pg
         self.p2p_host = self.backend == "gloo"
-        if halo in ("rccl", "tcp"):
+        if halo in ("rccl", "tcp", "ipc"):
             self.halo_lib, self.halo = self._start_cabi(halo, halo_port), halo      # explicit request: a failure is an error
         elif halo == "auto" and os.environ.get("NMP_HALO_AUTO", "1") != "0" and (
                 self.backend == "nccl" or os.environ.get("NMP_HALO_AUTO_TRANSPORT") == "tcp"):
@@ -138,14 +139,14 @@ class Comm:
     def _start_cabi(self, halo, halo_port):
         from . import abi
         lib = abi.load_library()
-        # bind the engine to THIS rank's GPU before anything of it touches a device: halo_init (RCCL transport) creates the
-        # engine's stream and the communicator on the current device, which would be GPU 0 for every rank otherwise
-        if halo == "rccl" or lib.noahmp_hip_device_count() > 0:
+        # bind the engine to THIS rank's GPU before anything of it touches a device: halo_init (RCCL / IPC transport) creates the
+        # engine's stream (and the communicator) on the current device, which would be GPU 0 for every rank otherwise
+        if halo in ("rccl", "ipc") or lib.noahmp_hip_device_count() > 0:
             rc = lib.noahmp_hip_set_device(self.device_index)
             if rc:
                 raise RuntimeError("noahmp_hip_set_device(%d): %s" % (self.device_index, lib.noahmp_hip_last_error().decode()))
         rc = lib.noahmp_hip_halo_init(self.rank, self.world, os.environ.get("MASTER_ADDR", "127.0.0.1").encode(), self._halo_port(halo_port),
-                                      abi.HALO_RCCL if halo == "rccl" else abi.HALO_TCP)
+                                      {"rccl": abi.HALO_RCCL, "ipc": abi.HALO_IPC}.get(halo, abi.HALO_TCP))
         if rc:
             raise RuntimeError("noahmp_hip_halo_init: rc=%d %s" % (rc, lib.noahmp_hip_last_error().decode()))
         return lib
@@ -260,7 +261,7 @@ class Comm:
         if not self.dist:
             return "none"
         if self.halo_lib is not None:
-            return "noahmp_hip_exchange_halo (%s transport, one phase)" % ("RCCL" if self.halo == "rccl" else "socket")
+            return "noahmp_hip_exchange_halo (%s transport, one phase)" % {"rccl": "RCCL", "ipc": "IPC"}.get(self.halo, "socket")
         import torch
         dist = self.dist
         bad = os.environ.get("NMP_HALO_FORCE_HOST") == "1"
@@ -328,7 +329,7 @@ class Comm:
 
     def _exchange_cabi(self, planes, geom):
         """The same exchange done by the engine library (noahmp_hip_exchange_halo): device planes on torch's current
-        stream, host planes (numpy arrays / CPU tensors) over its socket transport."""
+        stream, host planes (numpy arrays / CPU tensors) over its socket transport (the IPC transport takes device planes only)."""
         import ctypes as C
         import numpy as np
         from . import abi
@@ -336,6 +337,8 @@ class Comm:
         ptrs = (C.c_void_p * n)(*[(p.ctypes.data if isinstance(p, np.ndarray) else p.data_ptr()) for p in planes])
         idx = (C.c_int32 * 8)(*[geom[k] for k in ("ims", "ime", "jms", "jme", "its", "ite", "jts", "jte")])
         cuda = (not isinstance(planes[0], np.ndarray)) and planes[0].is_cuda
+        if self.halo == "ipc" and not all((not isinstance(p, np.ndarray)) and p.is_cuda for p in planes):
+            raise ValueError("halo='ipc' exchanges device-resident planes (torch tensors on the GPU); host planes need halo='tcp'")
         stream = None
         if cuda:
             import torch
