@@ -400,6 +400,68 @@ class Engine:
                 sc.nlev[i] = -sc.nlev[i]
         return sc
 
+    # ---- device-side history: interval accumulators and point probes (noahmp_history.hip; helper: noahmp_amd/history.py)
+    @staticmethod
+    def history_entries(entries):
+        """[(src tensor, acc tensor, op, scale), ...] -> a prepared (HistoryEntry * n) array; op = a NOAHMP_HIST_* value or its lower-case
+        name ("sum", "sum_dt", "min", "max", "last").  The tensors are kept alive by the returned array."""
+        n = len(entries)
+        arr = (abi.HistoryEntry * max(n, 1))()
+        for f, (src, acc, op, scale) in enumerate(entries):
+            arr[f].src = src.data_ptr() if src is not None else None
+            arr[f].acc = acc.data_ptr() if acc is not None else None
+            arr[f].nlev = acc.shape[1] if (acc is not None and acc.dim() == 3) else 1
+            arr[f].op = abi.HIST_OP[op] if isinstance(op, str) else int(op)
+            arr[f].scale = float(scale)
+        arr._n, arr._keep = n, list(entries)
+        return arr
+
+    @staticmethod
+    def history_probes(columns, fields, ring, slot=0):
+        """A noahmp_history_probes block: `columns` int32 device tensor (linear column indices in the block's current order), `fields` 2-D
+        device planes, `ring` float32 device tensor [nslot][nfield][npoint]."""
+        p = abi.HistoryProbes()
+        fp = (C.c_void_p * max(len(fields), 1))(*[t.data_ptr() for t in fields])
+        p.npoint, p.column, p.nfield, p.field, p.ring = int(columns.numel()), columns.data_ptr(), len(fields), fp, ring.data_ptr()
+        p.nslot, p.slot = int(ring.shape[0]), int(slot)
+        p._keep = (columns, list(fields), ring, fp)
+        return p
+
+    def history_step(self, entries, store, probes=None, count=None, stream=None):
+        """One sample of every accumulator and one ring slot of the probes after a step of `store` (a DeviceColumnStore, or a prepared
+        StepArgs block with device pointers): one kernel launch, enqueued only (noahmp_hip_history_step).  entries: history_entries(...)
+        or the list it takes; count: int32 device plane that counts the steps which advanced each column, or None."""
+        if not isinstance(entries, C.Array):
+            entries = Engine.history_entries(entries)
+        a = store if isinstance(store, abi.StepArgs) else store.step_args(1, 2000, 1.0)
+        rc = self.lib.noahmp_hip_history_step(entries._n, entries, C.byref(probes) if probes is not None else None, C.byref(a),
+                                              count.data_ptr() if count is not None else None, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_history_step: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
+    def history_finish(self, entries, dst, flags, count, store, perm=None, fill=None, mask_water=True, stream=None):
+        """Output-time finish (noahmp_hip_history_finish): dst[f] (tile-order device tensors, None = reset only) <- the accumulators,
+        flags[f] = "mean" / "reset" names or NOAHMP_HIST_FIN_* bits; perm = tile column -> position in the accumulators' order (the
+        inverse of what sort_store returned) or None; water points get -1.E33 (IVGTYP of `store`, which is in the accumulators' order).
+        Enqueued only; `count` is not cleared."""
+        from .restart import UNDEFINED
+        if not isinstance(entries, C.Array):
+            entries = Engine.history_entries(entries)
+        n = entries._n
+
+        def bits(f):
+            if isinstance(f, int):
+                return f
+            return sum(abi.HIST_FIN[x] for x in ((f,) if isinstance(f, str) else f))
+        dp = (C.c_void_p * max(n, 1))(*[(t.data_ptr() if t is not None else None) for t in dst])
+        fl = (C.c_uint32 * max(n, 1))(*[bits(f) for f in flags])
+        rc = self.lib.noahmp_hip_history_finish(n, entries, dp, fl, count.data_ptr() if count is not None else None,
+                                                perm.data_ptr() if perm is not None else None,
+                                                store.a["ivgtyp"].data_ptr() if mask_water else None, store.cfg.iswater,
+                                                float(UNDEFINED if fill is None else fill), store.ni, store.nj, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_history_finish: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

@@ -144,14 +144,30 @@ def write_restart(path, store, olddate, startdate=None, engine=None, perm=None, 
                   "RESTART FILE FROM HRLDAS ", restart=True, **attrs)
 
 
-def write_output(path, store, date, startdate=None, engine=None, perm=None, extra=None, **attrs):
+def write_output(path, store, date, startdate=None, engine=None, perm=None, extra=None, more=None, **attrs):
     """output.<date> / *.LDASOUT_DOMAIN* record (hrldas_output_prepare + the hrldas_output_add list, hdrv:690-812):
-    every real variable masked to -1.E33 on water points (put_var_2d with restart_flag false, put_var_3d)."""
+    every real variable masked to -1.E33 on water points (put_var_2d with restart_flag false, put_var_3d).
+
+    more: variables the reference's list does not have, appended after it: [(NAME, plane, layer kind, units), ...] with plane a
+    TILE-order numpy array or device tensor, (nj, ni) or (nj, levels, ni), layer kind None / "SOIL" / "SNOW" -- e.g. the finished
+    planes of noahmp_amd.history.History (already masked on water points: they are written as they are).  None: the reference's file,
+    byte for byte what this function wrote before it had the argument (`extra` only fills variables the list already has)."""
     names = [f for _, f, _, _ in OUTPUT_VARS]
     vals = fetch(engine, store, names, perm=perm, mask=names)
     if "zsnsoxy" in vals:
         vals = dict(vals, zsnsoxy=vals["zsnsoxy"][:, :NSNOW, :])
-    return _write(path, store, OUTPUT_VARS, vals, extra, date, startdate or date, "OUTPUT FROM HRLDAS ", restart=False, **attrs)
+    varlist = OUTPUT_VARS
+    if more:
+        have = {n for n, _, _, _ in OUTPUT_VARS}
+        varlist = list(OUTPUT_VARS)
+        vals = dict(vals)
+        for name, plane, lay, units in more:
+            assert name not in have, "write_output(more=): %s is already in the output file" % name
+            have.add(name)
+            key = "more:" + name
+            vals[key] = plane.detach().cpu().numpy() if hasattr(plane, "detach") else np.asarray(plane)
+            varlist.append((name, key, lay, units))
+    return _write(path, store, varlist, vals, extra, date, startdate or date, "OUTPUT FROM HRLDAS ", restart=False, **attrs)
 
 
 def _write(path, store, varlist, vals, extra, date, startdate, title, restart, version="v20150506", llanduse="USGS",

@@ -7,7 +7,13 @@ Parity at full size: columns are independent, so a random SAMPLE of columns is a
 through the same chain from the same raw state and the same forcing records, and compared bit for bit with the same
 columns of the full-size device run at a few checkpoints and at the end.
 
-usage: config5_run.py [ni nj [nsteps [nsample]]] [option=value ...]     default 3600 1800 720 4096, ModelConfig options
+usage: config5_run.py [ni nj [nsteps [nsample]]] [option=value ...] [--history[=DIR]]     default 3600 1800 720 4096, ModelConfig options
+
+--history (opt-in; DIR defaults to the working directory): the run keeps a device-side history (noahmp_amd/history.py) -- the four
+accumulators of the reference's WRF_HYDRO build (ACCPRCP, ACCECAN, ACCETRAN, ACCEDIR), the mean of HFX / LH / GRDFLX / FSA / FIRA and the
+minimum / maximum of T2MVXY per model day, one sample per step in one kernel launch -- and writes DIR/<date>.LDASOUT_DOMAIN1 once per
+model day: the reference's output record (restart.write_output) with those planes appended, after which the interval starts over.
+Writing is not part of the timed run.  The sample's accumulators are compared with the oracle's at the end, bit for bit.
 """
 import json
 import os
@@ -78,7 +84,7 @@ def fatal_column_vs_oracle(port, raw, lon, recs_tile, tcol, fail_step, e, cfgkw,
 
 
 def run(ni=3600, nj=1800, nsteps=720, nsample=4096, seed=5, verbose=True, checkpoints=(1, 24, 240), restart_path=None, cfgkw=None,
-        resort_every=24, resort_frac=0.10, lon_band=15.0):
+        resort_every=24, resort_frac=0.10, lon_band=15.0, history=None):
     T, tb = load_tables("usgs")
     port = PortLib(autobuild=not os.path.exists(os.path.join(ROOT, "oracle", "_build", "libnoahmp_oracle.so")))
     port.set_tables(T)
@@ -104,6 +110,17 @@ def run(ni=3600, nj=1800, nsteps=720, nsample=4096, seed=5, verbose=True, checkp
 
     lon_d, recs = sorted_side(perm)
     rain_d = torch.zeros((nj, ni), dtype=torch.float32, device=dev)
+    hist, hist_files, hist_acc = None, [], {}
+    if history is not None:                                            # opt-in: device-side history, written once per model day
+        from noahmp_amd.history import History, REFERENCE_ACCUMULATORS
+        os.makedirs(history, exist_ok=True)
+        hist = History(eng, d)
+        hist.add_reference_accumulators()
+        for nm, f in (("HFX", "hfx"), ("LH", "lh"), ("GRDFLX", "grdflx"), ("FSA", "fsaxy"), ("FIRA", "firaxy")):
+            hist.add(nm + "_MEAN", f, "sum", mean=True)
+        hist.add("T2MV_MIN", "t2mvxy", "min")
+        hist.add("T2MV_MAX", "t2mvxy", "max")
+        hist_units = dict(accprcp="mm", accecan="mm", accetran="mm", accedir="mm", T2MV_MIN="K", T2MV_MAX="K")
     n_land = int(((d.a["xland"] < 1.5) & (d.a["xice"] < raw.cfg.xice_thres)).sum().item())        # soil + glacier columns
 
     # ---- the sample: sorted positions, their tile columns, their raw state and forcing records
@@ -144,6 +161,8 @@ def run(ni=3600, nj=1800, nsteps=720, nsample=4096, seed=5, verbose=True, checkp
             iday, ihour = synth5.step_time(n)
             jul = eng.forcing_prep(d, lon_d, rain_d, iday, ihour, first_step=(n == 0), stream=sp, wait=False)
             eng.noahmplsm_async(d.step_args(n + 1, 2000, jul), stream=sp)
+            if hist is not None:
+                hist.step(stream=sp)
             resort_due = bool(resort_every) and (n + 1) % resort_every == 0 and n + 1 < nsteps
             if n + 1 in checkpoints or (n + 1) % 24 == 0 or resort_due:
                 try:
@@ -166,6 +185,22 @@ def run(ni=3600, nj=1800, nsteps=720, nsample=4096, seed=5, verbose=True, checkp
                     snaps[n + 1] = extract(d, inv[tile_cols_t].cpu().numpy())         # the sample's current sorted positions
                     ts.synchronize()
                     t0 += time.perf_counter() - t_hold                   # snapshots are not part of the run
+                if hist is not None and (n + 1) % 24 == 0:             # a model day is over: finish, write, start the next interval
+                    import datetime
+                    from noahmp_amd import restart
+                    t_hold = time.perf_counter()
+                    planes = hist.finish(stream=sp)
+                    for nm in REFERENCE_ACCUMULATORS:                  # the sample's columns, for the comparison with the oracle
+                        hist_acc.setdefault(nm, []).append(planes[nm].reshape(-1)[tile_cols_t].cpu().numpy())
+                    date = (datetime.datetime(2000, 6, 20) + datetime.timedelta(hours=n + 1)).strftime("%Y-%m-%d_%H:%M:%S")
+                    rain_tile = torch.empty(ni * nj, dtype=torch.float32, device=dev)
+                    rain_tile[perm.long()] = rain_d.reshape(-1)
+                    hist_files.append(restart.write_output(
+                        os.path.join(history, date[:13].replace("-", "").replace("_", "") + ".LDASOUT_DOMAIN1"), d, date, "2000-06-20_00:00:00",
+                        engine=eng, perm=perm, extra={"rainrate": rain_tile.reshape(nj, ni).cpu().numpy()},
+                        more=[(nm.upper(), pl, None, hist_units.get(nm, "W m{-2}")) for nm, pl in planes.items()]))
+                    ts.synchronize()
+                    t0 += time.perf_counter() - t_hold                   # output is not part of the run
                 if resort_due:                                         # inside the timed run: staleness, re-sort
                     ts.synchronize()
                     stale = eng.sort_staleness(d)
@@ -176,6 +211,8 @@ def run(ni=3600, nj=1800, nsteps=720, nsample=4096, seed=5, verbose=True, checkp
                         ri2, k2 = divmod(n + 1, synth5.RECORD_HOURS)       # records are in the store's column order: evaluate them again
                         rec_a, rec_b = (recs.at(ri2), recs.at(ri2 + 1)) if k2 else (None, None)
                         resorts += 1
+                        if hist is not None:
+                            hist.follow(d)
         ts.synchronize()
     wall = time.perf_counter() - t0
     restart_s = None
@@ -201,6 +238,21 @@ def run(ni=3600, nj=1800, nsteps=720, nsample=4096, seed=5, verbose=True, checkp
         jul = port.forcing_prep(osamp, lon_s, rain_s, iday, ihour, first_step=(n == 0))
         so = port.noahmplsm(osamp, n + 1, 2000, jul)
         assert so.code == 0, "oracle: fatal code %d" % so.code
+        if hist is not None:                                           # drv:736-739 on the sample, float32 as the reference computes it
+            if n % 24 == 0:
+                oacc = {nm: np.zeros((1, nsample), np.float32) for nm in REFERENCE_ACCUMULATORS}
+            adv = ~((osamp.a["xland"] - np.float32(1.5)) >= 0) & ~(osamp.a["xice"] >= np.float32(raw.cfg.xice_thres))
+            for nm, (f, op, scaled) in REFERENCE_ACCUMULATORS.items():
+                x = osamp.a[f] * np.float32(raw.cfg.dt) if scaled else osamp.a[f]
+                oacc[nm] = np.where(adv, oacc[nm] + x, oacc[nm]).astype(np.float32)
+            if (n + 1) % 24 == 0 and (n + 1) // 24 <= len(next(iter(hist_acc.values()), [])):
+                water = osamp.a["ivgtyp"] == raw.cfg.iswater
+                for nm in REFERENCE_ACCUMULATORS:
+                    want = np.where(water, np.float32(-1e33), oacc[nm]).ravel()
+                    same = np.array_equal(want.view(np.uint32), hist_acc[nm][(n + 1) // 24 - 1].view(np.uint32))
+                    ok_all &= same
+                    if not same:
+                        report.append((n + 1, False, ["history %s differs from the oracle's accumulator" % nm]))
         if n + 1 in snaps:
             skip = ("t2mvxy", "t2mbxy", "q2mvxy", "q2mbxy", "chv2xy", "chb2xy") if (cfgkw or {}).get("iopt_sfc") == 2 else ()
             ok, lines = exact_check(osamp, snaps[n + 1], skip=skip)      # OPT_SFC=2: FH2 undefined in the reference
@@ -215,7 +267,8 @@ def run(ni=3600, nj=1800, nsteps=720, nsample=4096, seed=5, verbose=True, checkp
                sample=nsample, sample_bit_identical=bool(ok_all), checkpoints=[c for c, _, _ in report],
                isnow_states_in_sample=isn, oracle_sample_s=round(t_or, 1),
                glacier_in_sample=int((osamp.a["ivgtyp"] == raw.cfg.isice).sum()),
-               water_in_sample=int((osamp.a["xland"] > 1.5).sum()), restart=restart_s)
+               water_in_sample=int((osamp.a["xland"] > 1.5).sum()), restart=restart_s,
+               history_files=len(hist_files) if hist is not None else None)
     if verbose:
         for c, ok, lines in report:
             print("checkpoint step %d: %s" % (c, "BIT-IDENTICAL" if ok else "DIFFERS\n  " + "\n  ".join(lines)))
@@ -224,10 +277,12 @@ def run(ni=3600, nj=1800, nsteps=720, nsample=4096, seed=5, verbose=True, checkp
 
 
 if __name__ == "__main__":
-    kw = {x.split("=")[0]: int(x.split("=")[1]) for x in sys.argv[1:] if "=" in x}
-    a = [int(x) for x in sys.argv[1:] if "=" not in x]
+    argv = [x for x in sys.argv[1:] if not x.startswith("--history")]
+    hist_dir = ([x.partition("=")[2] or "." for x in sys.argv[1:] if x.startswith("--history")] or [None])[-1]
+    kw = {x.split("=")[0]: int(x.split("=")[1]) for x in argv if "=" in x}
+    a = [int(x) for x in argv if "=" not in x]
     res = run(*(a[:2] if len(a) >= 2 else (3600, 1800)), nsteps=a[2] if len(a) > 2 else 720,
               nsample=a[3] if len(a) > 3 else 4096, restart_path=os.environ.get("NMP_RESTART_PATH"),
               cfgkw=kw or None, resort_frac=float(os.environ.get("NMP_RESORT_FRAC", "0.10")),
-              resort_every=int(os.environ.get("NMP_RESORT_EVERY", "24")))
+              resort_every=int(os.environ.get("NMP_RESORT_EVERY", "24")), history=hist_dir)
     sys.exit(0 if res["sample_bit_identical"] else 1)
