@@ -140,6 +140,82 @@ NMP_DEV float pow_half(float x) { return sqrtf(x); }
 NMP_DEV float pow_two(float x) { return x * x; }
 NMP_DEV float pow_neg_quarter(float x) { return 1.0f / sqrtf(sqrtf(x)); }
 #endif
+// x ** y for a positive finite y and a base that is exactly zero in much of the model (CANWATER's FWET of a canopy that holds no water:
+// 75 % of the calls of a CONUS-like run): powf returns +0 for both zeros (its early return, x * x).  Taken here by a select, with 1.0
+// in the zero lanes' place, so that those lanes do not send their whole wave through powf_'s two cold blocks in every step.
+NMP_DEV float nmp_powf_zero_base(float x, float y) {
+  const bool zero = x == 0.f;
+  const float r = nmp_powf(zero ? 1.f : x, y);
+  return zero ? 0.f : r;
+}
+
+// libm policy of an optimistic region (a stretch of the physics written once as impl<CHK>): Libm<true> is the calls above; Libm<false>
+// runs the unchecked forms of nmp_libm.hpp -- no test, no cold block inside the region's loops -- and collects in `suspect` whether any
+// call of this lane met an argument the checked form would have branched on.  The region's wrapper looks at the suspect words of the
+// whole wave once (wave_any) and, if one is set, throws the pass away and runs impl<true> for the wave: lanes that were not suspect
+// compute the same bits again, so nothing is selected per lane.  The option-specialised units use it (NMP_OPTIMISTIC_REGIONS); the
+// generic unit keeps the checked forms everywhere.
+// (-DNMP_OPTIMISTIC_REGIONS=0 / 1 overrides: 0 is the all-checked build of the same source, 1 lets the host emulation of the generic
+// source run the regions, tests/test_optimistic_regions.py)
+#ifndef NMP_OPTIMISTIC_REGIONS
+#if defined(NMP_FIXED_DVEG) && NMP_EXACT_LIBM
+#define NMP_OPTIMISTIC_REGIONS 1
+#else
+#define NMP_OPTIMISTIC_REGIONS 0
+#endif
+#endif
+template <bool CHK> struct Libm;
+template <> struct Libm<true> {
+  NMP_DEV float expf(float x) { return nmp_expf(x); }
+  NMP_DEV float logf(float x) { return nmp_logf(x); }
+  NMP_DEV float powf(float x, float y) { return nmp_powf(x, y); }
+  template <int N> NMP_DEV void expfN(const float* x, float* out) { nmp_expfN<N>(x, out); }
+  template <int N> NMP_DEV void logfN(const float* x, float* out) { nmp_logfN<N>(x, out); }
+  template <int N> NMP_DEV void powfN(const float* x, const float* y, float* out) { nmp_powfN<N>(x, y, out); }
+  template <int N> NMP_DEV void powf_pairN(const float* x, float y1, float y2, float* o1, float* o2) { nmp_powf_pairN<N>(x, y1, y2, o1, o2); }
+  NMP_DEV void pow_quarter2(float x1, float x2, float& r1, float& r2) { nmp::pow_quarter2(x1, x2, r1, r2); }
+  NMP_DEV float pow_half(float x) { return nmp::pow_half(x); }
+  NMP_DEV float pow_neg_quarter(float x) { return nmp::pow_neg_quarter(x); }
+};
+#if NMP_EXACT_LIBM
+template <> struct Libm<false> {
+  unsigned suspect = 0;
+  NMP_DEV float expf(float x) { NMP_CNT(0); return libm::expf_u_(x, suspect); }
+  NMP_DEV float logf(float x) { NMP_CNT(1); return libm::logf_u_(x, suspect); }
+  NMP_DEV float powf(float x, float y) { NMP_CNT(2); return libm::powf_u_(x, y, suspect); }
+  template <int N> NMP_DEV void expfN(const float* x, float* out) { for (int n = 0; n < N; n++) NMP_CNT(0); libm::expfN_u_<N>(x, out, suspect); }
+  template <int N> NMP_DEV void logfN(const float* x, float* out) { for (int n = 0; n < N; n++) NMP_CNT(1); libm::logfN_u_<N>(x, out, suspect); }
+  template <int N> NMP_DEV void powfN(const float* x, const float* y, float* out) { for (int n = 0; n < N; n++) NMP_CNT(2); libm::powfN_u_<N>(x, y, out, suspect); }
+  template <int N> NMP_DEV void powf_pairN(const float* x, float y1, float y2, float* o1, float* o2) {
+    for (int n = 0; n < 2 * N; n++) NMP_CNT(2);
+    libm::powf_pairN_u_<N>(x, y1, y2, o1, o2, suspect);
+  }
+  NMP_DEV void pow_quarter2(float x1, float x2, float& r1, float& r2) {
+    NMP_CNT(6); NMP_CNT(6);
+    const float x[2] = {x1, x2}, y[2] = {0.25f, 0.25f}; float o[2];
+    libm::powfN_u_<2>(x, y, o, suspect);
+    r1 = o[0]; r2 = o[1];
+  }
+  NMP_DEV float pow_half(float x) { NMP_CNT(6); return libm::powf_u_(x, 0.5f, suspect); }
+  NMP_DEV float pow_neg_quarter(float x) { NMP_CNT(6); return libm::powf_u_(x, -0.25f, suspect); }
+};
+#endif
+// host-emulation instrumentation (-DNMP_REGION_COUNT, tests/test_optimistic_regions.py): how often each region's redo ran
+// (0 VEGE_FLUX loop1, 1 BARE_FLUX loop3, 2 SOILWATER)
+#if defined(NMP_REGION_COUNT) && !defined(__HIP_DEVICE_COMPILE__)
+extern "C" { __attribute__((used, visibility("default"))) inline long nmp_region_redos[3] = {0, 0, 0}; }
+#define NMP_REDO(i) (nmp_region_redos[i]++)
+#else
+#define NMP_REDO(i) ((void)0)
+#endif
+// true if `flag` is set in any active lane of the wave (on the host: in this column)
+NMP_DEV bool wave_any(bool flag) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __ballot(flag) != 0;
+#else
+  return flag;
+#endif
+}
 
 // Phase timers (profiling build only, -DNMP_PHASE_TIMERS): the first active lane of every wave adds the shader-clock ticks since
 // its previous NMP_TIC to a per-phase counter (spread over 256 slots).  
@@ -313,6 +389,7 @@ struct Ctx {
   // canopy loop (lsm:3234; 0 without a canopy), [2 t + 1] = STOMATA bisection steps of both leaves (lsm:5413) -- the two trip counts
   // that differ from column to column.  Read back by the column sort (NOAHMP_SORT_COST): a wavefront runs as long as its slowest lane.
   unsigned char* cost;
+  int force_checked;   // set_option "force_checked_regions": every wave of an optimistic region takes the checked redo (debug; the generic unit ignores it)
 };
 NMP_DEV void record_cost(const Ctx& c, int which, int n) {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(NMP_COST_RECORD)       // experiment builds only: the stores cost the land kernel 1.2 % (r05)

@@ -344,7 +344,9 @@ struct MoState {
 
 // SFCDIF1 lsm:4061-4220
 // r_rhocp: float64 reciprocal of RHOAIR*CPAIR (the callers' loops divide by it once per iteration; div_rc, nmp_dev_common.hpp)
-NMP_DEV void sfcdif1(int& err, int iter, float sfctmp, double r_rhocp, float h, float qair, float zlvl,
+// lm: the libm policy (nmp_dev_common.hpp: Libm<CHK>) -- BARE_FLUX's loop runs it unchecked first
+template <class LM>
+NMP_DEV void sfcdif1(LM& lm, int& err, int iter, float sfctmp, double r_rhocp, float h, float qair, float zlvl,
                      float zpd, float z0m, float ur, float mpe, MoState& m, float& cm,
                      float& ch) {
   const float z0h = z0m;
@@ -352,8 +354,8 @@ NMP_DEV void sfcdif1(int& err, int iter, float sfctmp, double r_rhocp, float h, 
   float moz2, fmnew, fhnew, fh2new;
   if (zlvl <= zpd) { if (!err) err = NOAHMP_ERR_STABILITY_STOP; }
   if (iter == 1) {                     // zlvl, zpd, z0m are fixed over the caller's loop
-    m.tmpcm = nmp_logf((zlvl - zpd) / z0m);
-    m.tmpcm2 = nmp_logf((2.0f + z0m) / z0m);
+    m.tmpcm = lm.logf((zlvl - zpd) / z0m);
+    m.tmpcm2 = lm.logf((2.0f + z0m) / z0m);
   }
   const float tmpcm = m.tmpcm, tmpch = m.tmpcm, tmpch2 = m.tmpcm2;
   if (iter == 1) {
@@ -371,10 +373,10 @@ NMP_DEV void sfcdif1(int& err, int iter, float sfctmp, double r_rhocp, float h, 
   if (m.mozsgn >= 2) { m.moz = 0.f; m.fm = 0.f; m.fh = 0.f; moz2 = 0.f; m.fh2 = 0.f; }
   if (m.moz < 0.f) {
     float tmp1, tmp12;                       // the two X = (1-16 MOZ)**0.25 are independent: evaluate them interleaved
-    pow_quarter2(1.f - 16.f * m.moz, 1.f - 16.f * moz2, tmp1, tmp12);
+    lm.pow_quarter2(1.f - 16.f * m.moz, 1.f - 16.f * moz2, tmp1, tmp12);
     const float la[3] = {(1.f + tmp1 * tmp1) / 2.f, (1.f + tmp1) / 2.f, (1.f + tmp12 * tmp12) / 2.f};
     float lg[3];
-    nmp_logfN<3>(la, lg);                    // the LOGs are independent: one batch
+    lm.template logfN<3>(la, lg);            // the LOGs are independent: one batch
     const float tmp2 = lg[0], tmp3 = lg[1];
     fmnew = 2.f * tmp3 + tmp2 - 2.f * nmp_atanf_ge1(tmp1) + 1.5707963f;
     fhnew = 2 * tmp2;
@@ -400,6 +402,12 @@ NMP_DEV void sfcdif1(int& err, int iter, float sfctmp, double r_rhocp, float h, 
   cm = VKC * VKC / (cmfm * cmfm);
   ch = VKC * VKC / (cmfm * chfh);
   m.fv = ur * sqrtf(cm);
+}
+NMP_DEV void sfcdif1(int& err, int iter, float sfctmp, double r_rhocp, float h, float qair, float zlvl,
+                     float zpd, float z0m, float ur, float mpe, MoState& m, float& cm,
+                     float& ch) {
+  Libm<true> lm;
+  sfcdif1(lm, err, iter, sfctmp, r_rhocp, h, qair, zlvl, zpd, z0m, ur, mpe, m, cm, ch);
 }
 
 // SFCDIF2 lsm:4224-4422
@@ -602,13 +610,14 @@ struct VegFirst {   // what only iteration 1 needs (STOMATA / CANRES run there, 
 };
 
 // one pass of the loop body, lsm:3236-3456
-template <bool FIRST>
-NMP_DEV void vege_iter(const Ctx& c, VegLoop& L, const int iter, VegFirst* f) {
+// lm: the libm policy of SFCDIF1 and RAGRB (nmp_dev_common.hpp: Libm<CHK>); STOMATA / CANRES of iteration 1 keep the checked forms
+template <bool FIRST, bool CHK>
+NMP_DEV void vege_iter(Libm<CHK>& lm, const Ctx& c, VegLoop& L, const int iter, VegFirst* f) {
   const float MPE = 1E-6f;
   const float sfctmp = L.sfctmp, rhoair = L.rhoair, ur = L.ur, fveg = L.fveg, tg = L.tg;
   const float z0h = L.z0m, z0hg = L.z0mg, hcan = L.hcan;
   if (c.O.sfc == 1) {
-    sfcdif1(L.err, iter, sfctmp, L.r_rhocp, L.h, L.qair, L.zlvl, L.zpd, L.z0m, ur, MPE, L.mo, L.cm, L.ch);
+    sfcdif1(lm, L.err, iter, sfctmp, L.r_rhocp, L.h, L.qair, L.zlvl, L.zpd, L.z0m, ur, MPE, L.mo, L.cm, L.ch);
   } else {
     sfcdif2(iter, L.z0m, L.tah, L.thair, ur, L.czil, L.zlvl, L.cm, L.ch, L.mo.moz, L.wstar, L.mo.fv, L.rlogu);
     L.ch = div_rc(L.ch, L.r_ur);                      // CH / UR, CM / UR (lsm:3318-3319): UR is fixed over the loop
@@ -625,14 +634,14 @@ NMP_DEV void vege_iter(const Ctx& c, VegLoop& L, const int iter, VegFirst* f) {
       float molg = -1.f * powi3(L.mo.fv) / tmp1;
       mozg = nmp_min((L.zpd - L.z0mg) / molg, 1.f);
     }
-    if (mozg < 0.f) fhgnew = pow_neg_quarter(1.f - 15.f * mozg);
+    if (mozg < 0.f) fhgnew = lm.pow_neg_quarter(1.f - 15.f * mozg);
     else fhgnew = 1.f + 4.7f * mozg;
     if (FIRST) L.fhg = fhgnew;
     else L.fhg = 0.5f * (L.fhg + fhgnew);
-    float cwpc = pow_half(L.cwp * L.vaie * hcan * L.fhg);
+    float cwpc = lm.pow_half(L.cwp * L.vaie * hcan * L.fhg);
     const float ea[4] = {div_rc(-cwpc * z0hg, L.r_hcan), div_rc(-cwpc * (z0h + L.zpd), L.r_hcan), cwpc, -cwpc / 2.f};
     float ex[4];
-    nmp_expfN<4>(ea, ex);                    // the four EXPs of RAGRB are independent: one batch
+    lm.template expfN<4>(ea, ex);            // the four EXPs of RAGRB are independent: one batch
     float tmp1 = ex[0];
     float tmp2 = ex[1];
     float tmprah2 = hcan * ex[2] / cwpc * (tmp1 - tmp2);
@@ -716,64 +725,98 @@ NMP_DEV void vege_iter(const Ctx& c, VegLoop& L, const int iter, VegFirst* f) {
 }
 
 // iterations 2.. of a column until it exits or `last` has been run
-NMP_DEV void vege_run_until(const Ctx& c, VegLoop& L, int last) {
+template <bool CHK>
+NMP_DEV void vege_run_until(Libm<CHK>& lm, const Ctx& c, VegLoop& L, int last) {
 #pragma unroll 1
-  while (!L.done && L.iter <= last) vege_iter<false>(c, L, L.iter, nullptr);
+  while (!L.done && L.iter <= last) vege_iter<false>(lm, c, L, L.iter, nullptr);
 }
 
 // The plain runner: every lane iterates its own column to the end.
 struct SimpleLoop {
-  NMP_DEV void run(const Ctx& c, VegLoop& L, bool active) const {
-    if (active) vege_run_until(c, L, 20);
+  template <bool CHK>
+  NMP_DEV void run(Libm<CHK>& lm, const Ctx& c, VegLoop& L, bool active) const {
+    if (active) vege_run_until(lm, c, L, 20);
   }
 };
+
+// VEGE_FLUX lsm:3018-3589.  All threads call it (the runner may contain workgroup barriers); `canopy` says
+// whether this thread has a vegetated column to work on.
+// What loop1 starts from: everything of VegLoop / VegFirst that does not change during the loop, and the state the loop carries, read
+// from s (which loop1 does not write: a pass can be run again from here).
+NMP_DEV void vege_setup(const Ctx& c, const Parm& P, Col& s, const VegIn& q, float cmv, VegLoop& L, VegFirst& f) {
+  const noahmp_tables* T = c.T;
+  const int v = s.vegtyp - 1;
+  L = VegLoop{};
+  f = VegFirst{};
+  f.P = &P; f.v = v;
+  if (c.O.crs == 1) f.sp = stomata_rows(T, v);          // requested first: eleven table rows
+  const float fveg = s.fveg, ur = q.ur;
+  L.sfctmp = s.sfctmp; L.rhoair = s.rhoair; L.qair = s.qair; L.zlvl = q.zlvl; L.zpd = q.zpd; L.z0m = q.z0m;
+  L.ur = ur; L.z0mg = q.z0mg; L.cwp = q.cwp; L.fveg = fveg; L.rsurf = q.rsurf; L.eair = s.eair;
+  L.gammav = q.gammav; L.canliq = s.canliq; L.canice = s.canice; L.latheav = s.latheav; L.sav = s.sav;
+  L.fwet = s.fwet; L.sfcprs = s.sfcprs; L.thair = s.thair; L.czil = P.czil;
+  L.mo = MoState{0.f, 0.f, 0.f, 0.f, 0.1f, 0, 0.f, 0.f};
+  L.tv = s.tv; L.tg = s.tgv; L.tah = s.tah; L.eah = s.eah; L.ch = s.chv; L.cm = cmv;
+  L.r_rhocp = q.r_rhocp; L.r_gammav = q.r_gammav;
+  if (c.O.sfc != 1) { L.r_ur = rc64(ur); L.rlogu = sfcdif2_rlogu(L.z0m, L.zlvl); }
+  const double r_fveg = rc64(fveg);
+  L.vaie = nmp_min(6.f, div_rc(q.vai, r_fveg));
+  L.laisune = nmp_min(6.f, div_rc(q.laisun, r_fveg));
+  L.laishae = nmp_min(6.f, div_rc(q.laisha, r_fveg));
+  float t = tdc(L.tg), destg_unused;
+  esat_sel(t, L.estg, destg_unused);
+  L.hcan = s.htop;
+  L.r_hcan = rc64(L.hcan);
+  float uc = ur * nmp_logf(L.hcan / q.z0m) / nmp_logf(q.zlvl / q.z0m);
+  if ((L.hcan - q.zpd) <= 0.f) raise(s, NOAHMP_ERR_HCAN_LE_ZPD);
+  L.air = -q.emv * (1.f + (1.f - q.emv) * (1.f - q.emg)) * s.lwdn - q.emv * q.emg * SB * powi4(L.tg);
+  L.cir = (2.f - q.emv * (1.f - q.emg)) * q.emv * SB;
+  L.sqrt_dleaf_uc = sqrtf(P.dleaf / uc);          // loop-invariant factor of RB (lsm:4054)
+  L.irc = s.irc; L.shc = s.shc; L.evc = s.evc; L.tr = s.tr;
+  L.done = 0; L.iter = 1;
+  f.parsun = q.parsun; f.parsha = q.parsha; f.foln = s.foln; f.o2air = s.o2air; f.co2air = s.co2air; f.igs = s.igs; f.btran = s.btran;
+}
+// loop1 under one libm policy: iteration 1 (with STOMATA / CANRES), then the runner's iterations 2..20
+template <bool CHK, class Runner>
+NMP_DEV void vege_loop1(Libm<CHK>& lm, const Ctx& c, const Parm& P, Col& s, const VegIn& q, float cmv, float& psnsun, float& psnsha,
+                        const bool canopy, Runner& runner, VegLoop& L, int& bisections) {
+  L = VegLoop{};
+  L.done = 1;
+  bisections = 0;
+  if (canopy) {
+    VegFirst f;
+    vege_setup(c, P, s, q, cmv, L, f);
+    vege_iter<true>(lm, c, L, 1, &f);
+    psnsun = f.psnsun; psnsha = f.psnsha;           // only iteration 1 evaluates them: they come from the pass that is kept
+    bisections = f.bisections;
+  }
+  runner.run(lm, c, L, canopy);
+}
 
 // VEGE_FLUX lsm:3018-3589.  All threads call it (the runner may contain workgroup barriers); `canopy` says
 // whether this thread has a vegetated column to work on.
 template <class Runner>
 NMP_DEV void vege_flux(const Ctx& c, const Parm& P, Col& s, const VegIn& q, float& cmv, float& psnsun,
                        float& psnsha, const bool canopy, Runner& runner) {
-  const noahmp_tables* T = c.T;
   const float MPE = 1E-6f;
-  VegLoop L = {};
-  L.done = 1;
-  if (canopy) {
-    const int v = s.vegtyp - 1;
-    VegFirst f = {};
-    f.P = &P; f.v = v;
-    if (c.O.crs == 1) f.sp = stomata_rows(T, v);          // requested first: eleven table rows
-    const float fveg = s.fveg, ur = q.ur;
-    L.sfctmp = s.sfctmp; L.rhoair = s.rhoair; L.qair = s.qair; L.zlvl = q.zlvl; L.zpd = q.zpd; L.z0m = q.z0m;
-    L.ur = ur; L.z0mg = q.z0mg; L.cwp = q.cwp; L.fveg = fveg; L.rsurf = q.rsurf; L.eair = s.eair;
-    L.gammav = q.gammav; L.canliq = s.canliq; L.canice = s.canice; L.latheav = s.latheav; L.sav = s.sav;
-    L.fwet = s.fwet; L.sfcprs = s.sfcprs; L.thair = s.thair; L.czil = P.czil;
-    L.mo = MoState{0.f, 0.f, 0.f, 0.f, 0.1f, 0, 0.f, 0.f};
-    L.tv = s.tv; L.tg = s.tgv; L.tah = s.tah; L.eah = s.eah; L.ch = s.chv; L.cm = cmv;
-    L.r_rhocp = q.r_rhocp; L.r_gammav = q.r_gammav;
-    if (c.O.sfc != 1) { L.r_ur = rc64(ur); L.rlogu = sfcdif2_rlogu(L.z0m, L.zlvl); }
-    const double r_fveg = rc64(fveg);
-    L.vaie = nmp_min(6.f, div_rc(q.vai, r_fveg));
-    L.laisune = nmp_min(6.f, div_rc(q.laisun, r_fveg));
-    L.laishae = nmp_min(6.f, div_rc(q.laisha, r_fveg));
-    float t = tdc(L.tg), destg_unused;
-    esat_sel(t, L.estg, destg_unused);
-    L.hcan = s.htop;
-    L.r_hcan = rc64(L.hcan);
-    float uc = ur * nmp_logf(L.hcan / q.z0m) / nmp_logf(q.zlvl / q.z0m);
-    if ((L.hcan - q.zpd) <= 0.f) raise(s, NOAHMP_ERR_HCAN_LE_ZPD);
-    L.air = -q.emv * (1.f + (1.f - q.emv) * (1.f - q.emg)) * s.lwdn - q.emv * q.emg * SB * powi4(L.tg);
-    L.cir = (2.f - q.emv * (1.f - q.emg)) * q.emv * SB;
-    L.sqrt_dleaf_uc = sqrtf(P.dleaf / uc);          // loop-invariant factor of RB (lsm:4054)
-    L.irc = s.irc; L.shc = s.shc; L.evc = s.evc; L.tr = s.tr;
-    L.done = 0; L.iter = 1;
-    f.parsun = q.parsun; f.parsha = q.parsha; f.foln = s.foln; f.o2air = s.o2air; f.co2air = s.co2air; f.igs = s.igs; f.btran = s.btran;
-    vege_iter<true>(c, L, 1, &f);                       // iteration 1 (with STOMATA / CANRES)
-    psnsun = f.psnsun; psnsha = f.psnsha;
-    record_cost(c, 1, f.bisections);
-  } else {
-    record_cost(c, 1, 0);
+  VegLoop L;
+  int bisections;
+#if NMP_OPTIMISTIC_REGIONS
+  // The optimistic region "VEGE_FLUX loop1": s is written only after the loop, so a pass is thrown away by running the next one from
+  // vege_setup again -- an error the pass raised from garbage (L.err) goes with it.  The decision is wave-uniform; SimpleLoop has no
+  // workgroup barrier (a runner that has one must make the decision per workgroup).
+  Libm<false> u;
+  vege_loop1(u, c, P, s, q, cmv, psnsun, psnsha, canopy, runner, L, bisections);
+  if (__builtin_expect(wave_any(u.suspect != 0 || c.force_checked != 0), 0)) {
+    NMP_REDO(0);
+    Libm<true> lm;
+    vege_loop1(lm, c, P, s, q, cmv, psnsun, psnsha, canopy, runner, L, bisections);
   }
-  runner.run(c, L, canopy);                             // iterations 2..20
+#else
+  Libm<true> lm;
+  vege_loop1(lm, c, P, s, q, cmv, psnsun, psnsha, canopy, runner, L, bisections);
+#endif
+  record_cost(c, 1, canopy ? bisections : 0);
   record_cost(c, 0, canopy ? L.iter - 1 : 0);
   NMP_TIC(21);
   if (!canopy) return;
@@ -843,28 +886,28 @@ NMP_DEV void vege_flux(const Ctx& c, const Parm& P, Col& s, const VegIn& q, floa
 }
 
 // BARE_FLUX lsm:3591-3958
-NMP_DEV void bare_flux(const Ctx& c, const Parm& P, Col& s, const VegIn& q, float zpdg, float& cmb) {
+struct BareLoop {
+  double r_ur; float rlogu2;                          // fixed over loop3 (OPT_SFC = 2 only)
+  MoState mo; float h, wstar, estg, destg, csh, cev, ehb;      // carried from iteration to iteration / read after the loop
+};
+// loop3, written once for both libm policies (SFCDIF1's LOGs and X**0.25; SFCDIF2 keeps the checked forms under either).  Changes
+// TGB, CHB, CMB, the error word and B; the fluxes and QSFC it leaves in s are assigned, not updated.
+template <bool CHK>
+NMP_DEV void bare_loop3(Libm<CHK>& lm, const Ctx& c, const Parm& P, Col& s, const VegIn& q, float zpdg, float& cmb, BareLoop& B) {
   const float MPE = 1E-6f;
   const float rhoair = s.rhoair, sfctmp = s.sfctmp, ur = q.ur, z0m = q.z0mg;
-  MoState mo = {0.f, 0.f, 0.f, 0.f, 0.1f, 0, 0.f, 0.f};
-  float h = 0.f, wstar = 0.f;
-  float t, estg = 0.f, destg, csh = 0.f, cev = 0.f, ehb = 0.f;
-  float& tgb = s.tgb; float& ch = s.chb; float& cm = cmb;
-  const float z0h = z0m;
   const float cir = q.emg * SB;
   const float cgh = 2.f * q.df_top / q.dz_top;
-  const float gamma = q.gammag, lathea = s.latheag;
-  // ESAT of the ground temperature (lsm:3789, 3836): the call that follows TGB's update in one iteration has the argument of the call
-  // that opens the next one, so each TGB is evaluated once; the flux corrections by DTG and QSFC (lsm:3821-3824, 3842) are
-  // overwritten by the next iteration before anything reads them, so only the fifth evaluates them
-  t = tdc(tgb);
-  esat_sel(t, estg, destg);
-  const double r_ur = (c.O.sfc != 1) ? rc64(ur) : 0.0;
-  const float rlogu2 = (c.O.sfc != 1) ? sfcdif2_rlogu(z0m, q.zlvl) : 0.f;       // SFCDIF2's RLOGU: Z0M and ZLVL are fixed over loop3
+  MoState& mo = B.mo;
+  float& h = B.h; float& wstar = B.wstar; float& estg = B.estg; float& destg = B.destg; float& csh = B.csh; float& cev = B.cev; float& ehb = B.ehb;
+  float& tgb = s.tgb; float& ch = s.chb; float& cm = cmb;
+  const double r_ur = B.r_ur;
+  const float rlogu2 = B.rlogu2;
+  float t;
 #pragma unroll 1
   for (int iter = 1; iter <= 5; iter++) {               // loop3, NITERB = 5 (lsm:3749)
     if (c.O.sfc == 1) {
-      sfcdif1(s.err, iter, sfctmp, q.r_rhocp, h, s.qair, q.zlvl, zpdg, z0m, ur, MPE, mo, cm, ch);
+      sfcdif1(lm, s.err, iter, sfctmp, q.r_rhocp, h, s.qair, q.zlvl, zpdg, z0m, ur, MPE, mo, cm, ch);
     } else {
       sfcdif2(iter, z0m, tgb, s.thair, ur, P.czil, q.zlvl, cm, ch, mo.moz, wstar, mo.fv, rlogu2);
       ch = div_rc(ch, r_ur);                         // CH / UR, CM / UR (lsm:3776-3777)
@@ -896,6 +939,43 @@ NMP_DEV void bare_flux(const Ctx& c, const Parm& P, Col& s, const VegIn& q, floa
     esat_sel(t, estg, destg);
     if (iter == 5) s.qsfc = 0.622f * (estg * q.rhsur) / (s.psfc - 0.378f * (estg * q.rhsur));
   }
+}
+
+NMP_DEV void bare_flux(const Ctx& c, const Parm& P, Col& s, const VegIn& q, float zpdg, float& cmb) {
+  const float rhoair = s.rhoair, sfctmp = s.sfctmp, ur = q.ur, z0m = q.z0mg;
+  float& tgb = s.tgb; float& ch = s.chb;
+  const float z0h = z0m;
+  const float cir = q.emg * SB;
+  const float lathea = s.latheag;
+  BareLoop B = {};
+  B.mo = MoState{0.f, 0.f, 0.f, 0.f, 0.1f, 0, 0.f, 0.f};
+  // ESAT of the ground temperature (lsm:3789, 3836): the call that follows TGB's update in one iteration has the argument of the call
+  // that opens the next one, so each TGB is evaluated once; the flux corrections by DTG and QSFC (lsm:3821-3824, 3842) are
+  // overwritten by the next iteration before anything reads them, so only the fifth evaluates them
+  esat_sel(tdc(tgb), B.estg, B.destg);
+  B.r_ur = (c.O.sfc != 1) ? rc64(ur) : 0.0;
+  B.rlogu2 = (c.O.sfc != 1) ? sfcdif2_rlogu(z0m, q.zlvl) : 0.f;       // SFCDIF2's RLOGU: Z0M and ZLVL are fixed over loop3
+#if NMP_OPTIMISTIC_REGIONS
+  // The optimistic region "BARE_FLUX loop3": one pass with the unchecked libm forms; if a lane of the wave met a rare argument (or
+  // "force_checked_regions" is set) what the pass changed is put back -- an error it raised from garbage included, so that VEGE_FLUX's
+  // error still comes before BARE_FLUX's -- and the wave runs the checked pass.
+  const BareLoop B0 = B;
+  const float tgb0 = s.tgb, chb0 = s.chb, cmb0 = cmb;
+  const int err0 = s.err;
+  Libm<false> u;
+  bare_loop3(u, c, P, s, q, zpdg, cmb, B);
+  if (__builtin_expect(wave_any(u.suspect != 0 || c.force_checked != 0), 0)) {
+    NMP_REDO(1);
+    B = B0; s.tgb = tgb0; s.chb = chb0; cmb = cmb0; s.err = err0;
+    Libm<true> lm;
+    bare_loop3(lm, c, P, s, q, zpdg, cmb, B);
+  }
+#else
+  Libm<true> lm;
+  bare_loop3(lm, c, P, s, q, zpdg, cmb, B);
+#endif
+  const MoState& mo = B.mo;
+  const float estg = B.estg, csh = B.csh, cev = B.cev, ehb = B.ehb;
   if (c.O.stc == 1) {
     if (s.snowh > 0.05f && tgb > TFRZ) {
       tgb = TFRZ;

@@ -74,7 +74,7 @@ NMP_DEV void canwater(const Ctx& c, const Parm& P, Col& s, float& qrain, float& 
   if (s.canice <= 1.E-6f) s.canice = 0.f;
   if (s.canice > 0.f) s.fwet = nmp_max(0.f, s.canice) / nmp_max(maxsno, 1.E-06f);
   else s.fwet = nmp_max(0.f, s.canliq) / nmp_max(maxliq, 1.E-06f);
-  s.fwet = nmp_powf(nmp_min(s.fwet, 1.f), 0.667f);
+  s.fwet = nmp_powf_zero_base(nmp_min(s.fwet, 1.f), 0.667f);
   if (s.canice > 1.E-6f && s.tv > TFRZ) {
     float qmeltc = nmp_min(div_rc(s.canice, rdt), div_rc(div_rc((s.tv - TFRZ) * CICE * s.canice, NMP_RCC(DENICE)), c.u.dt_hfus));
     s.canice = nmp_max(0.f, s.canice - qmeltc * dt);
@@ -457,25 +457,28 @@ NMP_DEV void wdfcnd1(const Parm& P, double r_smcmax, float& wdf, float& wcnd, fl
   wcnd = P.dksat * nmp_powf(factr, 2.0f * P.bexp + 3.0f);
   wcnd = wcnd * (1.0f - fcr);
 }
-NMP_DEV void wdfcnd2(const Parm& P, double r_smcmax, float& wdf, float& wcnd, float smc, float sice) {
+template <class M>
+NMP_DEV void wdfcnd2(M& m, const Parm& P, double r_smcmax, float& wdf, float& wcnd, float smc, float sice) {
   float factr = nmp_max(0.01f, div_rc(smc, r_smcmax));
   float expon = P.bexp + 2.0f;
-  wdf = P.dwsat * nmp_powf(factr, expon);
+  wdf = P.dwsat * m.powf(factr, expon);
   if (sice > 0.0f) {
     float x = 500.f * sice;
-    float vkwgt = 1.f / (1.f + nmp_powf(x, 3.f));
-    wdf = vkwgt * wdf + (1.f - vkwgt) * P.dwsat * nmp_powf(div_rc(0.2f, r_smcmax), expon);
+    float vkwgt = 1.f / (1.f + m.powf(x, 3.f));
+    wdf = vkwgt * wdf + (1.f - vkwgt) * P.dwsat * m.powf(div_rc(0.2f, r_smcmax), expon);
   }
-  wcnd = P.dksat * nmp_powf(factr, 2.0f * P.bexp + 3.0f);
+  wcnd = P.dksat * m.powf(factr, 2.0f * P.bexp + 3.0f);
 }
 
 // SOILWATER lsm:7680-7936 with ZWTEQ (7938-7989), INFIL (7992-8087), SRT (8089-8217), SSTEP (8220-8327)
-template <class A>
-NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, float qinsur, float qseva,
-                       const float* etrani, float& qdrain, float* wcnd, float& fcrmax) {
+// Written once for both libm policies (nmp_dev_common.hpp: Libm<CHK>); reads the layer arrays y, leaves the new SH2O / SMC in
+// sh2o[] / smc[] for soilwater() below to store, and writes no other memory: a pass can be thrown away by restoring a few scalars of s.
+template <bool CHK, class A>
+NMP_DEV void soilwater_impl(Libm<CHK>& m, const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, float qinsur, float qseva,
+                            const float* etrani, float& qdrain, float* wcnd, float& fcrmax, float* sh2o, float* smc) {
   const float dt = c.dt;
   const double r_smcmax = rc64(P.smcmax);      // SMCMAX divides ~20 times below (FICE, WDFCND x 4 layers x NITER)
-  float sh2o[NL], smc[NL], sice[NL], dz[NL], fcr[NL];
+  float sice[NL], dz[NL], fcr[NL];
   float pddum = 0.0f, rsat = 0.0f, sicemax = 0.0f;
   s.runsrf = 0.0f;
   fcrmax = 0.0f;
@@ -494,7 +497,7 @@ NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, flo
   float fcr_arg[NSOIL], fcr_exp[NSOIL];
 #pragma unroll
   for (int k = 1; k <= NSOIL; k++) fcr_arg[k - 1] = -4.0f * (1.f - nmp_min(1.0f, div_rc(sice[L(k)], r_smcmax)));
-  nmp_expfN<NSOIL>(fcr_arg, fcr_exp);          // the four layers' EXP as one batch
+  m.template expfN<NSOIL>(fcr_arg, fcr_exp);          // the four layers' EXP as one batch
 #pragma unroll
   for (int k = 1; k <= NSOIL; k++) {
     fcr[L(k)] = div_rc(nmp_max(0.0f, fcr_exp[k - 1] - ea4), c.u.one_m_ea4);
@@ -512,17 +515,17 @@ NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, flo
     for (int k = 1; k <= 100; k++) {
       float zfine = (float)k * dzfine;
       float temp = 1.f + (zwt0 - zfine) / P.psisat;
-      wd2 = wd2 + P.smcmax * (1.f - nmp_powf(temp, -1.f / P.bexp)) * dzfine;
+      wd2 = wd2 + P.smcmax * (1.f - m.powf(temp, -1.f / P.bexp)) * dzfine;
       if (fabsf(wd2 - wd1) <= 0.01f) { s.zwt = zfine; break; }
     }
-    s.runsub = (1.0f - fcrmax) * 4.0f * nmp_expf_const(-TIMEAN) * nmp_expf(-2.0f * s.zwt);
+    s.runsub = (1.0f - fcrmax) * 4.0f * nmp_expf_const(-TIMEAN) * m.expf(-2.0f * s.zwt);
   }
   if (s.vegtyp == c.isurban) fcr[L(1)] = 0.95f;
   if (c.O.run == 1 || c.O.run == 2 || c.O.run == 4 || c.O.run == 5) {
     float fsat;
-    if (c.O.run == 1) fsat = FSATMX * nmp_expf(-0.5f * 6.0f * (s.zwt - 2.0f));
-    else if (c.O.run == 5) fsat = FSATMX * nmp_expf(-0.5f * 6.0f * nmp_max(-2.0f - s.zwt, 0.f));
-    else if (c.O.run == 2) fsat = FSATMX * nmp_expf(-0.5f * 2.0f * s.zwt);
+    if (c.O.run == 1) fsat = FSATMX * m.expf(-0.5f * 6.0f * (s.zwt - 2.0f));
+    else if (c.O.run == 5) fsat = FSATMX * m.expf(-0.5f * 6.0f * nmp_max(-2.0f - s.zwt, 0.f));
+    else if (c.O.run == 2) fsat = FSATMX * m.expf(-0.5f * 2.0f * s.zwt);
     else {
       float smctot = 0.f, dztot = 0.f;
       bool done = false;
@@ -535,7 +538,7 @@ NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, flo
         }
       }
       smctot = smctot / dztot;
-      fsat = nmp_powf(nmp_max(0.01f, smctot / P.smcmax), 4.f);
+      fsat = m.powf(nmp_max(0.01f, smctot / P.smcmax), 4.f);
     }
     if (qinsur > 0.f) {
       s.runsrf = qinsur * ((1.0f - fcr[L(1)]) * fsat + fcr[L(1)]);
@@ -558,7 +561,7 @@ NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, flo
         dmax = dmax * (1.0f - (sh2o[L(k)] + sice[L(k)] - P.smcwlt) / smcav);
         dd = dd + dmax;
       }
-      float val = (1.f - nmp_expf(-P.kdt * dt1));
+      float val = (1.f - m.expf(-P.kdt * dt1));
       float ddt = dd * val;
       float px = nmp_max(0.f, qinsur * dt);
       float infmax = (px * (ddt / (px + ddt))) / dt;
@@ -568,11 +571,11 @@ NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, flo
         float sum = 1.f;
         sum = sum + (acrt * acrt) / 2.f;                  // J=1: ACRT**2 / (2)
         sum = sum + acrt / 1.f;                           // J=2: ACRT**1 / 1
-        fcr_ = 1.f - nmp_expf(-acrt) * sum;
+        fcr_ = 1.f - m.expf(-acrt) * sum;
       }
       infmax = infmax * fcr_;
       float wdf_, wcnd_;
-      wdfcnd2(P, r_smcmax, wdf_, wcnd_, sh2o[L(1)], sicemax);
+      wdfcnd2(m, P, r_smcmax, wdf_, wcnd_, sh2o[L(1)], sicemax);
       infmax = nmp_max(infmax, wcnd_);
       infmax = nmp_min(infmax, px);
       s.runsrf = nmp_max(0.f, qinsur - infmax);
@@ -596,7 +599,7 @@ NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, flo
       float factr[NSOIL], pw1[NSOIL], pw2[NSOIL];
 #pragma unroll
       for (int k = 1; k <= NSOIL; k++) factr[k - 1] = nmp_max(0.01f, div_rc(smc[L(k)], r_smcmax));
-      nmp_powf_pairN<NSOIL>(factr, P.bexp + 2.0f, 2.0f * P.bexp + 3.0f, pw1, pw2);
+      m.template powf_pairN<NSOIL>(factr, P.bexp + 2.0f, 2.0f * P.bexp + 3.0f, pw1, pw2);
 #pragma unroll
       for (int k = 1; k <= NSOIL; k++) {
         wdf[L(k)] = P.dwsat * pw1[k - 1];
@@ -607,7 +610,7 @@ NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, flo
       }
     } else {
 #pragma unroll
-      for (int k = 1; k <= NSOIL; k++) { wdfcnd2(P, r_smcmax, wdf[L(k)], wcnd[L(k)], sh2o[L(k)], sicemax); smx[L(k)] = sh2o[L(k)]; }
+      for (int k = 1; k <= NSOIL; k++) { wdfcnd2(m, P, r_smcmax, wdf[L(k)], wcnd[L(k)], sh2o[L(k)], sicemax); smx[L(k)] = sh2o[L(k)]; }
     }
     if (c.O.run == 5) smxwtd = (c.O.inf == 1) ? s.smcwtd : s.smcwtd * sh2o[L(NSOIL)] / smc[L(NSOIL)];
 #pragma unroll
@@ -742,6 +745,31 @@ NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, flo
 #pragma unroll
     for (int iz = 1; iz <= NSOIL; iz++) sh2o[L(iz)] = div_rc(mliq[L(iz)], c.u.dzmm[L(iz)]);
   }
+}
+
+// The optimistic region "SOILWATER" (option-specialised units): one pass with the unchecked libm forms -- the sub-step loop is then a
+// single basic block -- and, if any lane of the wave met a rare argument (or "force_checked_regions" is set), the scalars of s the pass
+// had changed are put back and the whole wave runs the checked pass, which is the code every unit ran before and the generic unit still
+// runs alone.  SOILWATER raises no error of its own, so there is none to discard with the pass.
+template <class A>
+NMP_DEV void soilwater(const Ctx& c, const Parm& P, Col& s, const Lay<A>& y, float qinsur, float qseva,
+                       const float* etrani, float& qdrain, float* wcnd, float& fcrmax) {
+  float sh2o[NL], smc[NL];
+#if NMP_OPTIMISTIC_REGIONS
+  const float runsub0 = s.runsub, zwt0 = s.zwt, smcwtd0 = s.smcwtd, deeprech0 = s.deeprech;     // (RUNSRF is set, not updated; SOILWATER does not touch s.err)
+  Libm<false> u;
+  soilwater_impl(u, c, P, s, y, qinsur, qseva, etrani, qdrain, wcnd, fcrmax, sh2o, smc);
+  if (__builtin_expect(wave_any(u.suspect != 0 || c.force_checked != 0), 0)) {
+    NMP_REDO(2);
+    if (c.O.run != 1) s.runsub = runsub0;
+    if (c.O.run == 2 || c.O.run == 5) { s.zwt = zwt0; s.smcwtd = smcwtd0; s.deeprech = deeprech0; }
+    Libm<true> m;
+    soilwater_impl(m, c, P, s, y, qinsur, qseva, etrani, qdrain, wcnd, fcrmax, sh2o, smc);
+  }
+#else
+  Libm<true> m;
+  soilwater_impl(m, c, P, s, y, qinsur, qseva, etrani, qdrain, wcnd, fcrmax, sh2o, smc);
+#endif
 #pragma unroll
   for (int k = 1; k <= NSOIL; k++) { y.sh2o[L(k)] = sh2o[L(k)]; y.smc[L(k)] = smc[L(k)]; }
 }

@@ -21,7 +21,7 @@ static void NMP_CAT(fill_fixed_, NMP_FIXED_TAG)(KArgs& k, const LaunchDesc& d) {
   for (int l = 0; l < NL; l++) k.c.zsoil[l] = d.zsoil[l];
   ctx_fill_uniform(k.c);
   k.ni = d.ni; k.nka = d.nka; k.nti = d.nti; k.ntj = d.ntj; k.k1 = d.k1; k.kp_lo = d.kp_lo; k.kp_hi = d.kp_hi; k.yearlen = d.yearlen;
-  k.c.cost = d.cost;
+  k.c.cost = d.cost; k.c.force_checked = d.force_checked;
   k.r_land = d.r_land; k.r_ice = d.r_ice; k.r_skip = d.r_skip;
   k.err = d.err; k.counts = d.counts; k.err_base = d.err_base; k.t_offset = d.t_offset; k.t_first = d.t_first; k.t_count = d.t_count;
 }

@@ -99,6 +99,7 @@ struct Engine {
   noahmp_step_args resident_args;                        // the argument block of that call (for fetch)
   int jit_kernels = 1;          // compile a specialised kernel at run time (hiprtc, cached on disk) for option sets without an ahead-of-time one
   int jit_compile_only = 0;     // test hook: compile, do not load or launch (works without a GPU)
+  int force_checked_regions = 0;   // debug: the optimistic regions of the option-specialised kernels always redo with the checked libm forms
   int fixed_kernels = 1;        // use the option-specialised kernels when a call's options are the reference's namelist values
   long sorted_land = -1, sorted_glacier = -1;   // class ranges of a sorted device-resident layout (-1: not declared)
   int block = 256;             // 4 waves per workgroup: ~1 % faster than 64 at 1 M columns (bench); 64 and 128 selectable
@@ -121,6 +122,7 @@ struct LaunchDesc {
   long t_offset, t_first, t_count;
   unsigned char* cost;           // Ctx::cost of this launch (already offset to its first column) or NULL
   long r_land, r_ice, r_skip;    // mode 4 (noahmp_ranges_kernel): columns per class range
+  int force_checked;             // Ctx::force_checked
 };
 // mode: 0 mixed tile, 4 the three class ranges of a sorted layout in one launch; ev0 / ev1: the kernel's start / stop events or NULL;
 // d<DVEG>_r<RUN>, the other options = namelist values

@@ -205,6 +205,7 @@ int noahmp_hip_set_option(const char* key, int value) {
   else if (!strcmp(key, "jit_option_kernels")) { prev = g.jit_kernels; if (value == 0 || value == 1) g.jit_kernels = value; }
   else if (!strcmp(key, "jit_compile_only")) { prev = g.jit_compile_only; if (value == 0 || value == 1) g.jit_compile_only = value; }
   else if (!strcmp(key, "fixed_option_kernels")) { prev = g.fixed_kernels; if (value == 0 || value == 1) g.fixed_kernels = value; }
+  else if (!strcmp(key, "force_checked_regions")) { prev = g.force_checked_regions; if (value == 0 || value == 1) g.force_checked_regions = value; }
   else if (!strcmp(key, "sorted_land_columns")) { prev = (int)g.sorted_land; g.sorted_land = value; }
   else if (!strcmp(key, "sorted_glacier_columns")) { prev = (int)g.sorted_glacier; g.sorted_glacier = value; }
   else if (!strcmp(key, "resident_state")) {
@@ -321,7 +322,7 @@ static bool launch_fixed(const KArgs& k, int level, int mode, hipStream_t s, hip
   for (int l = 0; l < NL; l++) d.zsoil[l] = k.c.zsoil[l];
   d.ni = k.ni; d.nka = k.nka; d.nti = k.nti; d.ntj = k.ntj; d.k1 = k.k1; d.kp_lo = k.kp_lo; d.kp_hi = k.kp_hi; d.yearlen = k.yearlen;
   d.err = k.err; d.counts = k.counts; d.err_base = k.err_base; d.t_offset = k.t_offset; d.t_first = k.t_first; d.t_count = k.t_count;
-  d.cost = k.c.cost;
+  d.cost = k.c.cost; d.force_checked = g.force_checked_regions;
   d.r_land = k.r_land; d.r_ice = k.r_ice; d.r_skip = k.r_skip;
   if (level > 0) { kFixed[level - 1].launch(d, mode, s, ev0, ev1); return true; }
   const Opt& o = k.c.O;

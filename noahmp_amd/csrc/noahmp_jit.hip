@@ -68,6 +68,9 @@ const char* kBuildMacros =
 #ifdef NMP_PHASE_TIMERS
     "#define NMP_PHASE_TIMERS 1\n"
 #endif
+#ifdef NMP_LIBM_NO_SPECIAL
+    "#define NMP_LIBM_NO_SPECIAL 1\n"                  // profiling-only (nmp_libm.hpp)
+#endif
     ;
 // the wrapper around the headers (kernel names, launch bounds): part of the cache key like the headers themselves
 const char* kWrapper =
