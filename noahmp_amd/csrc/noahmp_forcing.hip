@@ -184,8 +184,10 @@ __global__ void __launch_bounds__(1024) noahmp_scatter_big_kernel(const ScatterA
       int sj = sj0, si = si0;
       asm volatile("" : "+v"(sj), "+v"(si));
       // elements go in groups of G with a scheduling barrier between groups: left alone, the compiler batches all R loads of a thread
-      // (R values + R 64-bit addresses) and spills 320 registers
-      constexpr int G = 8;
+      // (R values + R 64-bit addresses) and spills 320 registers.  G <= R: the 2048- and 4096-column chunks hold 2 and 4 elements per thread, and a
+      // group of 8 indexed dp[] / oj[] past their end -- undefined, and the sorted -> tile direction of those variants then stored nothing
+      // (tests/test_permute_gpu.py, 7 x 65000 and 1153 x 769)
+      constexpr int G = R < 8 ? R : 8;
       if (!k.reverse) {          // coalesced reads of consecutive tile cells, writes in ascending sorted position
 #pragma unroll
         for (int g0 = 0; g0 < R; g0 += G) {
