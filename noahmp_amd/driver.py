@@ -462,6 +462,78 @@ class Engine:
         if rc:
             raise RuntimeError("noahmp_hip_history_finish: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
+    # ---- region series: per-step weighted sums / minima / maxima over labelled regions (noahmp_regions.hip; helper: history.py::Regions)
+    class RegionPlan:
+        """The device workspace noahmp_hip_region_plan filled, and what a step on it needs."""
+
+        def __init__(self, plan, ni, nj, nregion):
+            self.plan, self.ni, self.nj, self.nregion = plan, ni, nj, nregion
+            self.scratch = None
+
+    def region_plan(self, region_map, nregion, weight=None, inv_perm=None, stream=None):
+        """Plan of the regions of a tile (noahmp_hip_region_plan): region_map = int32 device tensor (nj, ni) in TILE order, ids
+        0 .. nregion-1, negative = no region; weight = float32 device tensor in tile order or None (= 1); inv_perm[tile index] = position
+        of the cell in the block's current column order (int32 device tensor; None = tile order).  Built on the device; waits."""
+        import torch
+        nj, ni = region_map.shape
+        assert region_map.dtype == torch.int32 and (weight is None or weight.dtype == torch.float32)
+        words = C.c_int64(0)
+        rc = self.lib.noahmp_hip_region_plan_size(ni, nj, int(nregion), C.byref(words))
+        if rc:
+            raise RuntimeError("noahmp_hip_region_plan_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        plan = torch.empty((words.value + 1) // 2, dtype=torch.int64, device=region_map.device).view(torch.int32)
+        torch.cuda.current_stream().synchronize()
+        rc = self.lib.noahmp_hip_region_plan(region_map.data_ptr(), weight.data_ptr() if weight is not None else None, ni, nj, int(nregion),
+                                             inv_perm.data_ptr() if inv_perm is not None else None, plan.data_ptr(), plan.numel(), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_region_plan: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        return Engine.RegionPlan(plan, ni, nj, int(nregion))
+
+    def region_follow(self, rp, inv_perm, stream=None):
+        """After a re-sort: the members' positions for the new column order (noahmp_hip_region_plan_follow; enqueued only)."""
+        rc = self.lib.noahmp_hip_region_plan_follow(rp.plan.data_ptr(), inv_perm.data_ptr() if inv_perm is not None else None, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_region_plan_follow: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        rp.scratch = None
+
+    @staticmethod
+    def region_entries(entries):
+        """[(src tensor or None = the constant 1, op, level or None), ...] -> a prepared (RegionEntry * n) array; op = a NOAHMP_REG_* value
+        or "sum" / "min" / "max"; level: which level of a layered (nj, nlev, ni) array.  The tensors are kept alive by the array."""
+        n = len(entries)
+        arr = (abi.RegionEntry * max(n, 1))()
+        for f, (src, op, level) in enumerate(entries):
+            arr[f].src = src.data_ptr() if src is not None else None
+            arr[f].nlev = src.shape[1] if (src is not None and src.dim() == 3) else 1
+            arr[f].lev = int(level or 0)
+            arr[f].op = abi.REG_OP[op] if isinstance(op, str) else int(op)
+        arr._n, arr._keep = n, list(entries)
+        return arr
+
+    def region_scratch_bytes(self, rp, n):
+        b = C.c_int64(0)
+        rc = self.lib.noahmp_hip_region_scratch_size(rp.plan.data_ptr(), n, C.byref(b))
+        if rc:
+            raise RuntimeError("noahmp_hip_region_scratch_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        return int(b.value)
+
+    def region_step(self, rp, entries, store, series, slot, acc=None, stream=None):
+        """One ring slot of every entry after a step of `store` (a DeviceColumnStore or a prepared StepArgs block): series = float64 device
+        tensor [nslot][n][nregion], slot % nslot is written; acc = float64 [n][nregion] interval accumulators or None.  Enqueued only
+        (noahmp_hip_region_step); the scratch is allocated at the first call on a plan."""
+        import torch
+        if not isinstance(entries, C.Array):
+            entries = Engine.region_entries(entries)
+        a = store if isinstance(store, abi.StepArgs) else store.step_args(1, 2000, 1.0)
+        need = self.region_scratch_bytes(rp, entries._n)
+        if rp.scratch is None or rp.scratch.numel() * 8 < need:
+            rp.scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=rp.plan.device)
+            torch.cuda.current_stream().synchronize()
+        rc = self.lib.noahmp_hip_region_step(rp.plan.data_ptr(), entries._n, entries, C.byref(a), series.data_ptr(), int(series.shape[0]), int(slot),
+                                             acc.data_ptr() if acc is not None else None, rp.scratch.data_ptr(), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_region_step: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

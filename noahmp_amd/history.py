@@ -174,3 +174,120 @@ class History:
         out = np.stack([ring[s % nslot] for s in range(first, self.slot)]) if self.slot > first else ring[:0]
         self._read = self.slot
         return out
+
+
+class Regions:
+    """Per-step series of fields of the store over labelled regions -- basins, counties, land-use zones (noahmp_hip_region_step).
+
+        rg = Regions(engine, store, basin_map, nbasin, weight=cell_area, nslot=24)
+        rg.add("runoff", "runsfxy")                     # area-weighted sum per basin and step
+        rg.add("sm_top", "smois", level=0)
+        rg.add("t2_max", "t2mvxy", op="max")
+        for step in ...:
+            engine.noahmplsm_async(args); rg.step()
+            if sort happened: rg.follow(store)          # after Engine.sort_store(store)
+        series = rg.read()                              # {name: float64 [steps since the last read][nregion]}
+        means = rg.means()                              # the SUM series divided by the series of the summed weights
+
+    region_map: int32 (nj, ni) in TILE order whatever order the store is in (numpy or device tensor), ids 0 .. nregion-1, negative = no
+    region; weight: float32 (nj, ni) in tile order or None (= 1).  The result is a function of the tile-order values alone: the same bits in
+    tile order, in any sorted layout, before and after a re-sort.  Cells that the step does not advance (open water, sea ice) contribute
+    nothing.  A region that spans the tiles of several ranks: each rank returns its own sums and weight sums.  At most 31 series (one more,
+    the summed weights, is kept for means()); a ring of `nslot` steps between two read() calls."""
+
+    WEIGHT = "__weight__"
+
+    def __init__(self, engine, store, region_map, nregion, weight=None, nslot=24):
+        import torch
+        self.engine, self.store, self.torch = engine, store, torch
+        dev = store.device
+        self.region_map = torch.as_tensor(np.ascontiguousarray(region_map, dtype=np.int32) if isinstance(region_map, np.ndarray) else region_map,
+                                          device=dev).to(torch.int32).contiguous()
+        self.weight = None if weight is None else torch.as_tensor(
+            np.ascontiguousarray(weight, dtype=np.float32) if isinstance(weight, np.ndarray) else weight, device=dev).to(torch.float32).contiguous()
+        assert tuple(self.region_map.shape) == (store.nj, store.ni)
+        self.nregion, self.nslot = int(nregion), int(nslot)
+        self.items = [(self.WEIGHT, None, "sum", None)]          # [name, field, op, level]; entry 0: the summed weights of the cells that took part
+        self.slot = self._read = 0
+        self.series = self.acc = self._entries = None
+        torch.cuda.current_stream().synchronize()
+        self.plan = engine.region_plan(self.region_map, self.nregion, self.weight, self._inverse(getattr(store, "sort_perm", None)))
+
+    def _inverse(self, perm):
+        if perm is None:
+            return None
+        torch = self.torch
+        inv = torch.empty_like(perm)
+        inv[perm.long()] = torch.arange(perm.numel(), dtype=perm.dtype, device=perm.device)
+        torch.cuda.current_stream().synchronize()
+        return inv
+
+    def add(self, name, field, op="sum", level=None):
+        """A series of store field `field` (a 2-D plane, or level `level` of a layered array); op: "sum" (weighted), "min", "max"."""
+        assert self.slot == 0, "add series before the first step"
+        assert len(self.items) < 32, "at most 31 series per Regions (one launch)"
+        src = self.store.a[field]
+        assert src.dtype == self.torch.float32 and (src.dim() == 2 or level is not None)
+        self.items.append((name, field, op, level))
+        self._entries = None
+
+    def invalidate(self):
+        """The store's planes were replaced: look their addresses up again at the next step."""
+        self._entries = None
+
+    def _prepare(self):
+        torch, st = self.torch, self.store
+        n = len(self.items)
+        if self.series is None:
+            self.series = torch.zeros((self.nslot, n, self.nregion), dtype=torch.float64, device=st.device)
+            self.acc = torch.zeros((n, self.nregion), dtype=torch.float64, device=st.device)
+            self.reset_acc()
+        self._entries = self.engine.region_entries([(st.a[f] if f is not None else None, op, lev) for name, f, op, lev in self.items])
+        self._args = st.step_args(1, 2000, 1.0)
+        torch.cuda.current_stream().synchronize()
+
+    def reset_acc(self):
+        """Start the next interval: the accumulators (`acc`: sums of the series' sums, minima of minima, maxima of maxima) to their identities."""
+        for f, (name, field, op, lev) in enumerate(self.items):
+            self.acc[f].fill_({"sum": 0.0, "min": HUGE, "max": -HUGE}[op])
+        self.torch.cuda.current_stream().synchronize()
+
+    def step(self, stream=None):
+        """After a step of the store: one ring slot of every series (enqueued only)."""
+        if self._entries is None:
+            self._prepare()
+        self.engine.region_step(self.plan, self._entries, self._args, self.series, self.slot, acc=self.acc, stream=stream)
+        self.slot += 1
+
+    def follow(self, store=None):
+        """After Engine.sort_store(store): the members' positions in the store's new column order."""
+        if store is not None:
+            self.store = store
+        perm = getattr(self.store, "sort_perm", None)
+        assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
+        self.engine.region_follow(self.plan, self._inverse(perm))
+        self.engine.stream_sync()
+        self._entries = None
+
+    def read(self):
+        """{name: float64 numpy [steps][nregion]}: the steps since the last read (at most the ring's slots), oldest first.  Waits."""
+        self.engine.stream_sync()
+        first = max(self._read, self.slot - self.nslot)
+        n = len(self.items)
+        ring = self.series.cpu().numpy() if self.series is not None else np.zeros((self.nslot, n, self.nregion))
+        rec = np.stack([ring[s % self.nslot] for s in range(first, self.slot)]) if self.slot > first else ring[:0]
+        self._read = self.slot
+        self._last = {name: rec[:, f, :].copy() for f, (name, field, op, lev) in enumerate(self.items)}
+        return {k: v for k, v in self._last.items() if k != self.WEIGHT}
+
+    def means(self, series=None):
+        """The SUM series of the last read() (or of `series`, as read() returned it) divided by the summed weights of the cells that took
+        part: area-weighted means, NaN where no cell of the region took part."""
+        w = self._last[self.WEIGHT]
+        src = series if series is not None else self._last
+        out = {}
+        with np.errstate(all="ignore"):
+            for name, field, op, lev in self.items[1:]:
+                if op == "sum" and name in src:
+                    out[name] = src[name] / w
+        return out
