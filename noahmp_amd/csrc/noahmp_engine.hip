@@ -1174,6 +1174,7 @@ void noahmp_hip_finalize(void) {
 #endif
   nmp_host::sort_finalize();
   nmp_host::regions_finalize();
+  nmp_host::regrid_finalize();
   for (auto& p : g.gw_mirror) { if (p) hipFree(p); p = nullptr; }
   for (auto& p : g.init_mirror) { if (p) hipFree(p); p = nullptr; }
   for (auto e : g.async_events) hipEventDestroy(e);

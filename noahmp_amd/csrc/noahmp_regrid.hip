@@ -1,0 +1,275 @@
+// Forcing regrid of a device-resident run (no reference counterpart: the reference reads forcing already on the model grid, netcdf_io:1140;
+// the contract is the text in include/noahmp_hip.h, the arithmetic is nmp_dev_regrid.hpp).  With every resident option on, a 7 M-column
+// step spends more time in the 311 MB forcing upload than in the column kernel; real forcing arrives on a grid 50-150 times coarser than
+// the model's, so the coarse record is uploaded and the fine planes are made here.
+//
+// noahmp_hip_forcing_regrid: ONE launch per call.  A pure stream: per column 24 B of plan are read once and 4 B per entry written; the
+// corner reads go to source planes of a few hundred KB that stay in L2.  A thread owns four consecutive columns (16-byte loads of the plan
+// planes, 16-byte stores) and walks the entries itself, so the plan is paid once per column whatever n is; the corner loads of a batch of
+// entries are issued before the first store of the batch.  No LDS, no atomics.  Arrays are caller-owned: nothing is allocated, nothing waits.
+//
+// noahmp_hip_regrid_plan_latlon: one thread per target cell, once per run and tile.  The nearest-valid search runs only in the cells
+// whose four corners are masked out; the unfilled count is an integer atomic add of the cells that have none (rare).
+#include <string.h>
+#include <hip/hip_runtime.h>
+#include "noahmp_hip.h"
+#include "nmp_dev_regrid.hpp"
+#include "nmp_engine_host.hpp"
+
+using namespace nmp;
+using nmp_host::g;
+
+namespace {
+
+constexpr int kMaxEntries = NOAHMP_REGRID_MAX_ENTRIES;
+constexpr int kMaxRadius = 16;
+constexpr int kBlock = 256, kBatch = 2;
+
+struct RegridKArgs {                     // by value (< 1 KB): no engine-owned buffer, no copy per call
+  const float* src[kMaxEntries];
+  float* dst[kMaxEntries];
+  const float* adjust[kMaxEntries];
+  float scale[kMaxEntries];
+  float fill[kMaxEntries];
+  int mode[kMaxEntries];
+  const int* base; const int* near;
+  const float* w[4];
+  int n, nx, nxny, periodic;
+  int any_bilinear, any_nearest;
+  long ncell;
+};
+
+// what one column needs from the plan to serve every entry
+struct Col {
+  int idx[4];                            // corner indices (BILINEAR)
+  float w[4];
+  int near;
+  bool bil_ok, near_ok;
+};
+
+__device__ __forceinline__ Col make_col(const RegridKArgs& k, int base, int near, float w0, float w1, float w2, float w3) {
+  Col c;
+  c.w[0] = w0; c.w[1] = w1; c.w[2] = w2; c.w[3] = w3;
+  c.idx[0] = c.idx[1] = c.idx[2] = c.idx[3] = 0;
+  c.bil_ok = k.any_bilinear && regrid_corners(base, c.w, k.nx, k.nxny, k.periodic, c.idx);
+  c.near = near;
+  c.near_ok = k.any_nearest && regrid_near_ok(near, k.nxny);
+  return c;
+}
+
+// the loads of one entry and column: a corner of weight zero, and every corner of a column that receives fill, is not read
+__device__ __forceinline__ void load_corners(const RegridKArgs& k, int f, const Col& c, float* s) {
+  const float* __restrict__ src = k.src[f];
+  if (k.mode[f] == NOAHMP_REGRID_BILINEAR) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) s[q] = (c.bil_ok && c.w[q] != 0.f) ? src[c.idx[q]] : 0.f;
+  } else {
+    s[0] = c.near_ok ? src[c.near] : 0.f;
+  }
+}
+
+__device__ __forceinline__ float value(const RegridKArgs& k, int f, const Col& c, const float* s, float adj) {
+  float v;
+  if (k.mode[f] == NOAHMP_REGRID_BILINEAR) {
+    if (!c.bil_ok) return k.fill[f];
+    v = regrid_bilinear(c.w, s);
+  } else {
+    if (!c.near_ok) return k.fill[f];
+    v = s[0];
+  }
+  return k.adjust[f] ? regrid_adjust(v, k.scale[f], adj) : v;
+}
+
+// VEC: the plan planes, every dst and every adjust are 16-byte aligned and ncell is a multiple of four
+template <bool VEC>
+__global__ void __launch_bounds__(kBlock) noahmp_regrid_kernel(const RegridKArgs k) {
+  const long t = (long)blockIdx.x * kBlock + threadIdx.x;
+  constexpr int NC = VEC ? 4 : 1;
+  const long c0 = t * NC;
+  if (c0 >= k.ncell) return;
+  Col col[NC];
+  if constexpr (VEC) {
+    int4 b4 = make_int4(-1, -1, -1, -1), n4 = make_int4(-1, -1, -1, -1);
+    float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = w0, w2 = w0, w3 = w0;
+    if (k.any_bilinear) {
+      b4 = *(const int4*)(k.base + c0);
+      w0 = *(const float4*)(k.w[0] + c0); w1 = *(const float4*)(k.w[1] + c0);
+      w2 = *(const float4*)(k.w[2] + c0); w3 = *(const float4*)(k.w[3] + c0);
+    }
+    if (k.any_nearest) n4 = *(const int4*)(k.near + c0);
+    col[0] = make_col(k, b4.x, n4.x, w0.x, w1.x, w2.x, w3.x);
+    col[1] = make_col(k, b4.y, n4.y, w0.y, w1.y, w2.y, w3.y);
+    col[2] = make_col(k, b4.z, n4.z, w0.z, w1.z, w2.z, w3.z);
+    col[3] = make_col(k, b4.w, n4.w, w0.w, w1.w, w2.w, w3.w);
+  } else {
+    int b = -1, nr = -1;
+    float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
+    if (k.any_bilinear) { b = k.base[c0]; w0 = k.w[0][c0]; w1 = k.w[1][c0]; w2 = k.w[2][c0]; w3 = k.w[3][c0]; }
+    if (k.any_nearest) nr = k.near[c0];
+    col[0] = make_col(k, b, nr, w0, w1, w2, w3);
+  }
+  for (int f0 = 0; f0 < k.n; f0 += kBatch) {
+    // the corner loads of a batch of entries are in flight before its first store (planes may alias as far as the compiler knows)
+    float s[kBatch][NC][4];
+    float adj[kBatch][NC];
+#pragma unroll
+    for (int u = 0; u < kBatch; u++) {
+      const int f = f0 + u;
+      if (f >= k.n) break;
+#pragma unroll
+      for (int q = 0; q < NC; q++) load_corners(k, f, col[q], s[u][q]);
+      if constexpr (VEC) {
+        float4 a4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (k.adjust[f]) a4 = *(const float4*)(k.adjust[f] + c0);
+        adj[u][0] = a4.x; adj[u][1] = a4.y; adj[u][2] = a4.z; adj[u][3] = a4.w;
+      } else {
+        adj[u][0] = k.adjust[f] ? k.adjust[f][c0] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kBatch; u++) {
+      const int f = f0 + u;
+      if (f >= k.n) break;
+      if constexpr (VEC) {
+        float4 o;
+        o.x = value(k, f, col[0], s[u][0], adj[u][0]);
+        o.y = value(k, f, col[1], s[u][1], adj[u][1]);
+        o.z = value(k, f, col[2], s[u][2], adj[u][2]);
+        o.w = value(k, f, col[3], s[u][3], adj[u][3]);
+        *(float4*)(k.dst[f] + c0) = o;
+      } else {
+        k.dst[f][c0] = value(k, f, col[0], s[u][0], adj[u][0]);
+      }
+    }
+  }
+}
+
+struct PlanKArgs {
+  const float* xlat; const float* xlon;
+  const unsigned char* valid;
+  int* plan;
+  int* unfilled;
+  long ncell;
+  int nx, ny, periodic, radius;
+  double lon0, lat0, dlon, dlat;
+};
+
+__global__ void __launch_bounds__(kBlock) noahmp_regrid_plan_kernel(const PlanKArgs k) {
+  const long c = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= k.ncell) return;
+  const RegridCell r = regrid_plan_cell(k.xlat[c], k.xlon[c], k.nx, k.ny, k.lon0, k.lat0, k.dlon, k.dlat, k.periodic, k.valid, k.radius);
+  k.plan[c] = r.base;
+  k.plan[k.ncell + c] = r.near;
+#pragma unroll
+  for (int q = 0; q < 4; q++) k.plan[(2 + q) * k.ncell + c] = __float_as_int(r.w[q]);
+  if (r.base < 0) atomicAdd(k.unfilled, 1);
+}
+
+int check_source(const char* who, const noahmp_regrid_source* src) {
+  char b[200];
+  if (!src) { snprintf(b, sizeof b, "%s: the source grid is NULL", who); g.last_error = b; return -105; }
+  if (src->nx < 2 || src->ny < 2 || (long)src->nx * src->ny > (1L << 30)) {
+    snprintf(b, sizeof b, "%s: the source grid needs nx, ny >= 2 and nx*ny <= 2^30 (nx = %d, ny = %d)", who, src->nx, src->ny);
+    g.last_error = b; return -105;
+  }
+  return 0;
+}
+
+inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+int* h_unfilled = nullptr;               // page-locked landing place of the unfilled count
+
+}  // namespace
+
+namespace nmp_host {
+void regrid_finalize() {
+  if (h_unfilled) hipHostFree(h_unfilled);
+  h_unfilled = nullptr;
+}
+}  // namespace nmp_host
+
+extern "C" {
+
+int noahmp_hip_regrid_plan_size(int ni, int nj, int64_t* words) {
+  if (ni < 0 || nj < 0 || (long)ni * nj > 0x7FFFFFFFL || !words) {
+    g.last_error = "noahmp_hip_regrid_plan_size: 0 .. 2^31 - 1 cells and a place for the size";
+    return -105;
+  }
+  *words = 6 * (int64_t)ni * nj + 1;
+  return 0;
+}
+
+int noahmp_hip_regrid_plan_latlon(const float* xlat, const float* xlon, int ni, int nj, const noahmp_regrid_source* src,
+                                  const uint8_t* valid_src, int search_radius, int32_t* plan, int64_t plan_words, int32_t* unfilled,
+                                  void* stream) {
+  static const char* who = "noahmp_hip_regrid_plan_latlon";
+  char b[200];
+  int rc = check_source(who, src);
+  if (rc) return rc;
+  if (!(src->dlon > 0.0) || !(src->dlat != 0.0)) { snprintf(b, sizeof b, "%s: dlon > 0 and dlat != 0 are required", who); g.last_error = b; return -105; }
+  if (search_radius < 0 || search_radius > kMaxRadius) { snprintf(b, sizeof b, "%s: search_radius 0..%d (%d)", who, kMaxRadius, search_radius); g.last_error = b; return -105; }
+  const long ncell = (long)ni * nj;
+  if (ni < 0 || nj < 0 || ncell > 0x7FFFFFFFL) { snprintf(b, sizeof b, "%s: 0 .. 2^31 - 1 cells", who); g.last_error = b; return -105; }
+  if (!plan || (ncell > 0 && (!xlat || !xlon))) { snprintf(b, sizeof b, "%s: xlat, xlon and plan are required", who); g.last_error = b; return -105; }
+  if (plan_words < 6 * (int64_t)ncell + 1) {
+    snprintf(b, sizeof b, "%s: the workspace has %lld words, noahmp_hip_regrid_plan_size asks for %lld", who, (long long)plan_words, (long long)(6 * (int64_t)ncell + 1));
+    g.last_error = b; return -105;
+  }
+  rc = nmp_host::ensure_init();
+  if (rc) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  if (!h_unfilled) HIPCHK(hipHostMalloc((void**)&h_unfilled, sizeof(int), hipHostMallocDefault));
+  PlanKArgs k;
+  memset(&k, 0, sizeof(k));
+  k.xlat = xlat; k.xlon = xlon; k.valid = valid_src; k.plan = plan; k.unfilled = plan + 6 * ncell; k.ncell = ncell;
+  k.nx = src->nx; k.ny = src->ny; k.periodic = src->periodic_x ? 1 : 0; k.radius = search_radius;
+  k.lon0 = src->lon0; k.lat0 = src->lat0; k.dlon = src->dlon; k.dlat = src->dlat;
+  HIPCHK(hipMemsetAsync(k.unfilled, 0, sizeof(int), s));
+  if (ncell > 0) hipLaunchKernelGGL(noahmp_regrid_plan_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h_unfilled, k.unfilled, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (unfilled) *unfilled = *h_unfilled;
+  return 0;
+}
+
+int noahmp_hip_forcing_regrid(const int32_t* plan, int64_t ncell, const noahmp_regrid_source* src, int n, const noahmp_regrid_entry* e,
+                              void* stream) {
+  static const char* who = "noahmp_hip_forcing_regrid";
+  char b[200];
+  if (n < 0 || n > kMaxEntries) { snprintf(b, sizeof b, "%s: 0..%d entries per call (n = %d)", who, kMaxEntries, n); g.last_error = b; return -107; }
+  int rc = check_source(who, src);
+  if (rc) return rc;
+  if (ncell < 0 || ncell > 0x7FFFFFFFL) { snprintf(b, sizeof b, "%s: 0 .. 2^31 - 1 columns", who); g.last_error = b; return -105; }
+  if (!plan) { snprintf(b, sizeof b, "%s: the plan is NULL", who); g.last_error = b; return -105; }
+  if (n > 0 && !e) { snprintf(b, sizeof b, "%s: entries are NULL", who); g.last_error = b; return -105; }
+  for (int f = 0; f < n; f++) {
+    if (e[f].mode < NOAHMP_REGRID_BILINEAR || e[f].mode > NOAHMP_REGRID_NEAREST) {
+      snprintf(b, sizeof b, "%s: entry %d has mode %d (NOAHMP_REGRID_BILINEAR, NOAHMP_REGRID_NEAREST)", who, f, e[f].mode); g.last_error = b; return -105;
+    }
+    if (!e[f].src || !e[f].dst) { snprintf(b, sizeof b, "%s: entry %d has a NULL plane", who, f); g.last_error = b; return -105; }
+  }
+  rc = nmp_host::ensure_init();
+  if (rc) return rc;
+  if (n == 0 || ncell == 0) return 0;
+  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  RegridKArgs k;
+  memset(&k, 0, sizeof(k));
+  bool vec = aligned16(plan) && (ncell & 3) == 0;
+  for (int f = 0; f < n; f++) {
+    k.src[f] = e[f].src; k.dst[f] = e[f].dst; k.adjust[f] = e[f].adjust; k.scale[f] = e[f].scale; k.fill[f] = e[f].fill; k.mode[f] = e[f].mode;
+    if (e[f].mode == NOAHMP_REGRID_BILINEAR) k.any_bilinear = 1; else k.any_nearest = 1;
+    vec = vec && aligned16(e[f].dst) && aligned16(e[f].adjust);
+  }
+  k.base = plan; k.near = plan + ncell;
+  for (int q = 0; q < 4; q++) k.w[q] = (const float*)(plan + (2 + q) * ncell);
+  k.n = n; k.nx = src->nx; k.nxny = src->nx * src->ny; k.periodic = src->periodic_x ? 1 : 0; k.ncell = ncell;
+  const long nthread = vec ? ncell / 4 : ncell;
+  const unsigned blocks = (unsigned)((nthread + kBlock - 1) / kBlock);
+  if (vec) hipLaunchKernelGGL(noahmp_regrid_kernel<true>, dim3(blocks), dim3(kBlock), 0, s, k);
+  else hipLaunchKernelGGL(noahmp_regrid_kernel<false>, dim3(blocks), dim3(kBlock), 0, s, k);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

@@ -534,6 +534,60 @@ class Engine:
         if rc:
             raise RuntimeError("noahmp_hip_region_step: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
+    # ---- forcing regrid: coarse records -> the model grid's planes (noahmp_regrid.hip; helper: noahmp_amd/regrid.py)
+    @staticmethod
+    def regrid_source(nx, ny, lon0, lat0, dlon, dlat, periodic_x=False):
+        """A noahmp_regrid_source block: regular lat-lon grid, (lon0, lat0) = centre of cell (0, 0), dlat may be negative."""
+        g = abi.RegridSource()
+        g.nx, g.ny, g.lon0, g.lat0, g.dlon, g.dlat, g.periodic_x = int(nx), int(ny), float(lon0), float(lat0), float(dlon), float(dlat), int(bool(periodic_x))
+        return g
+
+    def regrid_plan(self, xlat, xlon, source, valid=None, search_radius=4, stream=None):
+        """Plan of a tile against a source grid (noahmp_hip_regrid_plan_latlon): xlat / xlon float32 device tensors (nj, ni) in TILE order,
+        valid = uint8 device tensor over the source grid or None.  Returns (plan, unfilled): the int32 workspace -- planes base, near,
+        w0..w3 of ni*nj words each, then the count word -- and the number of cells without a source.  Built on the device; waits."""
+        import torch
+        nj, ni = xlat.shape
+        assert xlat.dtype == torch.float32 and xlon.dtype == torch.float32 and xlat.is_contiguous() and xlon.is_contiguous()
+        assert valid is None or (valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == source.nx * source.ny)
+        words = C.c_int64(0)
+        rc = self.lib.noahmp_hip_regrid_plan_size(ni, nj, C.byref(words))
+        if rc:
+            raise RuntimeError("noahmp_hip_regrid_plan_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        plan = torch.empty(words.value, dtype=torch.int32, device=xlat.device)
+        torch.cuda.current_stream().synchronize()
+        unfilled = C.c_int32(0)
+        rc = self.lib.noahmp_hip_regrid_plan_latlon(xlat.data_ptr(), xlon.data_ptr(), ni, nj, C.byref(source),
+                                                    valid.data_ptr() if valid is not None else None, int(search_radius), plan.data_ptr(),
+                                                    plan.numel(), C.byref(unfilled), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_regrid_plan_latlon: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        return plan, int(unfilled.value)
+
+    @staticmethod
+    def regrid_entries(entries):
+        """[(src tensor, dst tensor, mode, adjust tensor or None, scale, fill), ...] -> a prepared (RegridEntry * n) array; mode = a
+        NOAHMP_REGRID_* value or "bilinear" / "nearest".  The tensors are kept alive by the returned array."""
+        n = len(entries)
+        arr = (abi.RegridEntry * max(n, 1))()
+        for f, (src, dst, mode, adjust, scale, fill) in enumerate(entries):
+            arr[f].src = src.data_ptr() if src is not None else None
+            arr[f].dst = dst.data_ptr() if dst is not None else None
+            arr[f].adjust = adjust.data_ptr() if adjust is not None else None
+            arr[f].scale, arr[f].fill = float(scale), float(fill)
+            arr[f].mode = abi.REGRID_MODE[mode] if isinstance(mode, str) else int(mode)
+        arr._n, arr._keep = n, list(entries)
+        return arr
+
+    def forcing_regrid(self, plan, ncell, source, entries, stream=None):
+        """Every entry's source plane -> its destination plane through `plan` (the workspace regrid_plan returned, or one the caller
+        filled or permuted): one kernel launch, enqueued only (noahmp_hip_forcing_regrid)."""
+        if not isinstance(entries, C.Array):
+            entries = Engine.regrid_entries(entries)
+        rc = self.lib.noahmp_hip_forcing_regrid(plan.data_ptr(), int(ncell), C.byref(source), entries._n, entries, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_forcing_regrid: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""
