@@ -11,6 +11,7 @@
 #include <math.h>
 #endif
 #include "noahmp_hip.h"
+#include "nmp_libm.hpp"
 
 namespace nmp {
 
@@ -155,6 +156,81 @@ NMP_DEV float regrid_adjust(float v, float scale, float adj) {
 #endif
   const float prod = scale * adj;
   return v + prod;
+}
+
+// ---- the met group of noahmp_hip_forcing_regrid_met: t, p, q, lw moved from the source's terrain height to the model's (Cosgrove et
+// al. 2003).  Every line is one rounded float32 operation of the header text; expf_ / powf_ are the checked forms of nmp_libm.hpp
+// (glibc's bits).  No guards: what the arithmetic gives for unphysical operands is the result.
+struct RegridMet {
+  float t, p, q, lw;
+};
+
+// saturation vapour pressure over water [Pa]
+NMP_DEV float regrid_met_esat(float t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float a = t - 273.15f;
+  const float num = 17.67f * a;
+  const float den = t - 29.65f;
+  const float x = num / den;
+  return 611.2f * libm::expf_(x);
+}
+
+// saturation specific humidity from esat(t) and the pressure
+NMP_DEV float regrid_met_qsat(float es, float p) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float num = 0.622f * es;
+  const float part = 0.378f * es;
+  const float den = p - part;
+  return num / den;
+}
+
+// clear-sky emissivity (Satterlund 1979) from specific humidity, pressure and temperature
+NMP_DEV float regrid_met_emis(float q, float p, float t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float qp = q * p;
+  const float e = qp / 0.622f;
+  const float mb = e / 100.0f;
+  const float ex = t / 2016.0f;
+  const float pw = libm::powf_(mb, ex);
+  const float en = libm::expf_(-pw);
+  const float one = 1.0f - en;
+  return 1.08f * one;
+}
+
+// (tc, pc, qc, lc) at the source's height -> the four values d metres higher; has_lw false: lc is passed through and no emissivity is made
+NMP_DEV RegridMet regrid_met(float tc, float pc, float qc, float lc, float d, float lapse, bool has_lw) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  RegridMet r;
+  r.t = tc; r.p = pc; r.q = qc; r.lw = lc;
+  if (d == 0.f) return r;                                    // either sign; a NaN d goes on and makes NaN
+  const float tf = regrid_adjust(tc, lapse, d);
+  const float tsum = tc + tf;
+  const float tbar = tsum * 0.5f;
+  const float gd = 9.81f * d;
+  const float rt = 287.0f * tbar;
+  const float hx = gd / rt;
+  const float pf = pc / libm::expf_(hx);
+  const float esc = regrid_met_esat(tc), esf = regrid_met_esat(tf);
+  const float rh = qc / regrid_met_qsat(esc, pc);
+  const float qf = rh * regrid_met_qsat(esf, pf);
+  r.t = tf; r.p = pf; r.q = qf;
+  if (has_lw) {
+    const float er = regrid_met_emis(qf, pf, tf) / regrid_met_emis(qc, pc, tc);
+    const float le = lc * er;
+    const float tf2 = tf * tf, tc2 = tc * tc;
+    const float tf4 = tf2 * tf2, tc4 = tc2 * tc2;
+    const float tr = tf4 / tc4;
+    r.lw = le * tr;
+  }
+  return r;
 }
 
 }  // namespace nmp

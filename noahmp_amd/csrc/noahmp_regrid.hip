@@ -8,9 +8,15 @@
 // planes, 16-byte stores) and walks the entries itself, so the plan is paid once per column whatever n is; the corner loads of a batch of
 // entries are issued before the first store of the batch.  No LDS, no atomics.  Arrays are caller-owned: nothing is allocated, nothing waits.
 //
+// noahmp_hip_forcing_regrid_met: the same kernel with a prologue in front of the entry loop (template parameter MET) that serves the met group
+// -- t, p, q, lw regridded bilinearly and moved to the model's terrain height (nmp_dev_regrid.hpp::regrid_met: five expf_ and two powf_ per
+// column, float64 inside) -- so a record still costs one launch.  All corner loads of the group and the dz load are issued before the first
+// libm call; the only LDS is the 768 B of libm tables.  The MET = false instantiations are the kernels of noahmp_hip_forcing_regrid, unchanged.
+//
 // noahmp_hip_regrid_plan_latlon: one thread per target cell, once per run and tile.  The nearest-valid search runs only in the cells
 // whose four corners are masked out; the unfilled count is an integer atomic add of the cells that have none (rare).
 #include <string.h>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 #include "noahmp_hip.h"
 #include "nmp_dev_regrid.hpp"
@@ -38,6 +44,16 @@ struct RegridKArgs {                     // by value (< 1 KB): no engine-owned b
   int any_bilinear, any_nearest;
   long ncell;
 };
+
+// the met group rides behind the entries' block: the MET = false kernels take RegridKArgs alone
+struct RegridMetKArgs : RegridKArgs {
+  const float* msrc[4];                  // t, p, q, lw (lw: NULL without longwave)
+  float* mdst[4];
+  const float* dz;
+  float lapse, mfill;
+  int has_lw;
+};
+template <bool MET> using KArgsOf = std::conditional_t<MET, RegridMetKArgs, RegridKArgs>;
 
 // what one column needs from the plan to serve every entry
 struct Col {
@@ -80,9 +96,35 @@ __device__ __forceinline__ float value(const RegridKArgs& k, int f, const Col& c
   return k.adjust[f] ? regrid_adjust(v, k.scale[f], adj) : v;
 }
 
+// The met group of one column: every corner load of its three or four sources and the dz load first, then the chain, then the stores.
+__device__ __forceinline__ void met_group(const RegridMetKArgs& k, const Col& col, long c) {
+  float s[4][4];
+#pragma unroll
+  for (int f = 0; f < 4; f++) {
+    const float* __restrict__ src = k.msrc[f];
+    const bool have = f < 3 || k.has_lw;
+#pragma unroll
+    for (int j = 0; j < 4; j++) s[f][j] = (have && col.bil_ok && col.w[j] != 0.f) ? src[col.idx[j]] : 0.f;
+  }
+  const float d = k.dz[c];
+  __builtin_amdgcn_sched_barrier(0);     // the loads above are in flight before the first libm call
+  RegridMet r;
+  r.t = r.p = r.q = r.lw = k.mfill;
+  if (col.bil_ok)
+    r = regrid_met(regrid_bilinear(col.w, s[0]), regrid_bilinear(col.w, s[1]), regrid_bilinear(col.w, s[2]), regrid_bilinear(col.w, s[3]), d,
+                   k.lapse, k.has_lw != 0);
+  k.mdst[0][c] = r.t; k.mdst[1][c] = r.p; k.mdst[2][c] = r.q;
+  if (k.has_lw) k.mdst[3][c] = r.lw;
+}
+
 // VEC: the plan planes, every dst and every adjust are 16-byte aligned and ncell is a multiple of four
-template <bool VEC>
-__global__ void __launch_bounds__(kBlock) noahmp_regrid_kernel(const RegridKArgs k) {
+// MET: noahmp_hip_forcing_regrid_met -- the met group in front of the unchanged entry loop.  Always one column per thread: with four the
+// 64 corner values of a thread are live together (137 VGPRs, 3 waves per SIMD against 46 and 8) and the launch measured 18-38 % slower
+// (DESIGN.md section 6), so <true, true> is never instantiated.
+template <bool VEC, bool MET>
+__global__ void __launch_bounds__(kBlock) noahmp_regrid_kernel(const KArgsOf<MET> k) {
+  static_assert(!(VEC && MET), "the met group runs one column per thread");
+  if constexpr (MET) libm::libm_stage_tables();      // holds a __syncthreads(): every thread of the workgroup, before any return
   const long t = (long)blockIdx.x * kBlock + threadIdx.x;
   constexpr int NC = VEC ? 4 : 1;
   const long c0 = t * NC;
@@ -108,6 +150,7 @@ __global__ void __launch_bounds__(kBlock) noahmp_regrid_kernel(const RegridKArgs
     if (k.any_nearest) nr = k.near[c0];
     col[0] = make_col(k, b, nr, w0, w1, w2, w3);
   }
+  if constexpr (MET) met_group(k, col[0], c0);
   for (int f0 = 0; f0 < k.n; f0 += kBatch) {
     // the corner loads of a batch of entries are in flight before its first store (planes may alias as far as the compiler knows)
     float s[kBatch][NC][4];
@@ -181,6 +224,68 @@ int* h_unfilled = nullptr;               // page-locked landing place of the unf
 
 }  // namespace
 
+namespace {
+
+// both regrid calls: the checks, then ONE launch (with_met: noahmp_hip_forcing_regrid_met)
+int regrid_call(const char* who, const int32_t* plan, int64_t ncell, const noahmp_regrid_source* src, bool with_met, const noahmp_regrid_met* met,
+                int n, const noahmp_regrid_entry* e, void* stream) {
+  char b[200];
+  if (n < 0 || n > kMaxEntries) { snprintf(b, sizeof b, "%s: 0..%d entries per call (n = %d)", who, kMaxEntries, n); g.last_error = b; return -107; }
+  int rc = check_source(who, src);
+  if (rc) return rc;
+  if (ncell < 0 || ncell > 0x7FFFFFFFL) { snprintf(b, sizeof b, "%s: 0 .. 2^31 - 1 columns", who); g.last_error = b; return -105; }
+  if (!plan) { snprintf(b, sizeof b, "%s: the plan is NULL", who); g.last_error = b; return -105; }
+  if (n > 0 && !e) { snprintf(b, sizeof b, "%s: entries are NULL", who); g.last_error = b; return -105; }
+  for (int f = 0; f < n; f++) {
+    if (e[f].mode < NOAHMP_REGRID_BILINEAR || e[f].mode > NOAHMP_REGRID_NEAREST) {
+      snprintf(b, sizeof b, "%s: entry %d has mode %d (NOAHMP_REGRID_BILINEAR, NOAHMP_REGRID_NEAREST)", who, f, e[f].mode); g.last_error = b; return -105;
+    }
+    if (!e[f].src || !e[f].dst) { snprintf(b, sizeof b, "%s: entry %d has a NULL plane", who, f); g.last_error = b; return -105; }
+  }
+  if (with_met) {
+    if (!met) { snprintf(b, sizeof b, "%s: met is NULL", who); g.last_error = b; return -105; }
+    if (!met->src_t || !met->src_p || !met->src_q || !met->dst_t || !met->dst_p || !met->dst_q || !met->dz) {
+      snprintf(b, sizeof b, "%s: met needs src_t, src_p, src_q, dst_t, dst_p, dst_q and dz", who); g.last_error = b; return -105;
+    }
+    if (met->src_lw && !met->dst_lw) { snprintf(b, sizeof b, "%s: met has src_lw but no dst_lw", who); g.last_error = b; return -105; }
+  }
+  rc = nmp_host::ensure_init();
+  if (rc) return rc;
+  if ((n == 0 && !with_met) || ncell == 0) return 0;
+  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  RegridMetKArgs k;                      // the MET = false kernels receive its RegridKArgs part
+  memset(&k, 0, sizeof(k));
+  bool vec = aligned16(plan) && (ncell & 3) == 0;
+  if (with_met) {
+    k.msrc[0] = met->src_t; k.msrc[1] = met->src_p; k.msrc[2] = met->src_q; k.msrc[3] = met->src_lw;
+    k.mdst[0] = met->dst_t; k.mdst[1] = met->dst_p; k.mdst[2] = met->dst_q; k.mdst[3] = met->src_lw ? met->dst_lw : nullptr;
+    k.dz = met->dz; k.lapse = met->lapse; k.mfill = met->fill; k.has_lw = met->src_lw ? 1 : 0;
+    k.any_bilinear = 1;
+    vec = false;
+  }
+  for (int f = 0; f < n; f++) {
+    k.src[f] = e[f].src; k.dst[f] = e[f].dst; k.adjust[f] = e[f].adjust; k.scale[f] = e[f].scale; k.fill[f] = e[f].fill; k.mode[f] = e[f].mode;
+    if (e[f].mode == NOAHMP_REGRID_BILINEAR) k.any_bilinear = 1; else k.any_nearest = 1;
+    vec = vec && aligned16(e[f].dst) && aligned16(e[f].adjust);
+  }
+  k.base = plan; k.near = plan + ncell;
+  for (int q = 0; q < 4; q++) k.w[q] = (const float*)(plan + (2 + q) * ncell);
+  k.n = n; k.nx = src->nx; k.nxny = src->nx * src->ny; k.periodic = src->periodic_x ? 1 : 0; k.ncell = ncell;
+  const long nthread = vec ? ncell / 4 : ncell;
+  const unsigned blocks = (unsigned)((nthread + kBlock - 1) / kBlock);
+  const RegridKArgs& kk = k;
+  if (with_met) {
+    hipLaunchKernelGGL((noahmp_regrid_kernel<false, true>), dim3(blocks), dim3(kBlock), 0, s, k);
+  } else {
+    if (vec) hipLaunchKernelGGL((noahmp_regrid_kernel<true, false>), dim3(blocks), dim3(kBlock), 0, s, kk);
+    else hipLaunchKernelGGL((noahmp_regrid_kernel<false, false>), dim3(blocks), dim3(kBlock), 0, s, kk);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
 namespace nmp_host {
 void regrid_finalize() {
   if (h_unfilled) hipHostFree(h_unfilled);
@@ -235,41 +340,12 @@ int noahmp_hip_regrid_plan_latlon(const float* xlat, const float* xlon, int ni, 
 
 int noahmp_hip_forcing_regrid(const int32_t* plan, int64_t ncell, const noahmp_regrid_source* src, int n, const noahmp_regrid_entry* e,
                               void* stream) {
-  static const char* who = "noahmp_hip_forcing_regrid";
-  char b[200];
-  if (n < 0 || n > kMaxEntries) { snprintf(b, sizeof b, "%s: 0..%d entries per call (n = %d)", who, kMaxEntries, n); g.last_error = b; return -107; }
-  int rc = check_source(who, src);
-  if (rc) return rc;
-  if (ncell < 0 || ncell > 0x7FFFFFFFL) { snprintf(b, sizeof b, "%s: 0 .. 2^31 - 1 columns", who); g.last_error = b; return -105; }
-  if (!plan) { snprintf(b, sizeof b, "%s: the plan is NULL", who); g.last_error = b; return -105; }
-  if (n > 0 && !e) { snprintf(b, sizeof b, "%s: entries are NULL", who); g.last_error = b; return -105; }
-  for (int f = 0; f < n; f++) {
-    if (e[f].mode < NOAHMP_REGRID_BILINEAR || e[f].mode > NOAHMP_REGRID_NEAREST) {
-      snprintf(b, sizeof b, "%s: entry %d has mode %d (NOAHMP_REGRID_BILINEAR, NOAHMP_REGRID_NEAREST)", who, f, e[f].mode); g.last_error = b; return -105;
-    }
-    if (!e[f].src || !e[f].dst) { snprintf(b, sizeof b, "%s: entry %d has a NULL plane", who, f); g.last_error = b; return -105; }
-  }
-  rc = nmp_host::ensure_init();
-  if (rc) return rc;
-  if (n == 0 || ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
-  RegridKArgs k;
-  memset(&k, 0, sizeof(k));
-  bool vec = aligned16(plan) && (ncell & 3) == 0;
-  for (int f = 0; f < n; f++) {
-    k.src[f] = e[f].src; k.dst[f] = e[f].dst; k.adjust[f] = e[f].adjust; k.scale[f] = e[f].scale; k.fill[f] = e[f].fill; k.mode[f] = e[f].mode;
-    if (e[f].mode == NOAHMP_REGRID_BILINEAR) k.any_bilinear = 1; else k.any_nearest = 1;
-    vec = vec && aligned16(e[f].dst) && aligned16(e[f].adjust);
-  }
-  k.base = plan; k.near = plan + ncell;
-  for (int q = 0; q < 4; q++) k.w[q] = (const float*)(plan + (2 + q) * ncell);
-  k.n = n; k.nx = src->nx; k.nxny = src->nx * src->ny; k.periodic = src->periodic_x ? 1 : 0; k.ncell = ncell;
-  const long nthread = vec ? ncell / 4 : ncell;
-  const unsigned blocks = (unsigned)((nthread + kBlock - 1) / kBlock);
-  if (vec) hipLaunchKernelGGL(noahmp_regrid_kernel<true>, dim3(blocks), dim3(kBlock), 0, s, k);
-  else hipLaunchKernelGGL(noahmp_regrid_kernel<false>, dim3(blocks), dim3(kBlock), 0, s, k);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return regrid_call("noahmp_hip_forcing_regrid", plan, ncell, src, false, nullptr, n, e, stream);
+}
+
+int noahmp_hip_forcing_regrid_met(const int32_t* plan, int64_t ncell, const noahmp_regrid_source* src, const noahmp_regrid_met* met, int n,
+                                  const noahmp_regrid_entry* e, void* stream) {
+  return regrid_call("noahmp_hip_forcing_regrid_met", plan, ncell, src, true, met, n, e, stream);
 }
 
 }  // extern "C"

@@ -588,6 +588,28 @@ class Engine:
         if rc:
             raise RuntimeError("noahmp_hip_forcing_regrid: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
+    @staticmethod
+    def regrid_met(src_t, src_p, src_q, dst_t, dst_p, dst_q, dz, src_lw=None, dst_lw=None, lapse=-0.0065, fill=float("nan")):
+        """A noahmp_regrid_met block: the elevation-adjusted group of noahmp_hip_forcing_regrid_met.  src_*: coarse device planes, dst_* and
+        dz (model height - regridded source height, metres): ncell values in the plan's column order.  The tensors are kept alive by the
+        returned block."""
+        m = abi.RegridMet()
+        keep = dict(src_t=src_t, src_p=src_p, src_q=src_q, src_lw=src_lw, dst_t=dst_t, dst_p=dst_p, dst_q=dst_q, dst_lw=dst_lw, dz=dz)
+        for name, t in keep.items():
+            setattr(m, name, t.data_ptr() if t is not None else None)
+        m.lapse, m.fill = float(lapse), float(fill)
+        m._keep = keep
+        return m
+
+    def forcing_regrid_met(self, plan, ncell, source, met, entries, stream=None):
+        """forcing_regrid with a met group (Engine.regrid_met): t, p, q and optionally lw regridded and moved to the model's terrain height,
+        plus the 0..32 ordinary entries, in one kernel launch, enqueued only (noahmp_hip_forcing_regrid_met)."""
+        if not isinstance(entries, C.Array):
+            entries = Engine.regrid_entries(entries)
+        rc = self.lib.noahmp_hip_forcing_regrid_met(plan.data_ptr(), int(ncell), C.byref(source), C.byref(met), entries._n, entries, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_forcing_regrid_met: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

@@ -2,7 +2,8 @@
 
     src = Engine.regrid_source(nx, ny, lon0, lat0, dlon, dlat, periodic_x=False)
     rg = ForcingRegrid(engine, xlat, xlon, src, valid=None, search_radius=4)      # builds the plan; rg.unfilled
-    rg.set_adjust("t", z_model - rg.regrid_plane(z_source), scale=-0.0065)       # optional: lapse-rate correction
+    rg.set_adjust("t", z_model - rg.regrid_plane(z_source), scale=-0.0065)       # optional: lapse-rate correction of one plane, or
+    rg.set_elevation(z_model, z_source, lapse=-0.0065)                           # optional: t, p, q, lw moved to the model's terrain height
     rec = rg.record({"t": t_c, "q": q_c, ..., "pcp": p_c}, modes={"pcp": "nearest"})
     rg.follow(store)          # after Engine.sort_store: plan and adjust planes go into the store's column order
 
@@ -29,6 +30,8 @@ class ForcingRegrid:
         self.adjust_tile, self.adjust = {}, {}   # name -> (plane, scale)
         self.sets = [{}, {}]                     # two sets of output planes, used alternately
         self.turn = 0
+        self.dz_tile = self.dz = None            # set_elevation: model height - regridded source height, tile order / current order
+        self.lapse = 0.0
 
     def _check_source_plane(self, t, name):
         assert t.dtype == self.torch.float32 and t.is_contiguous() and t.numel() == self.source.nx * self.source.ny, \
@@ -49,19 +52,42 @@ class ForcingRegrid:
         """Records' plane `name` receives + scale * plane: `plane` is an (nj, ni) device tensor in the CURRENT column order (what
         regrid_plane returns), e.g. model height - regridded source height with scale = -0.0065 K/m for the air temperature."""
         torch = self.torch
+        if name == "t" and self.dz is not None:
+            raise ValueError("set_adjust('t', ...) and set_elevation exclude each other: the met group makes the lapse-rate correction itself")
         plane = plane.to(torch.float32).contiguous()
         assert plane.numel() == self.ncell
         self.adjust[name] = (plane, float(scale))
+        self.adjust_tile[name] = (self._tile_order(plane), float(scale))
+        torch.cuda.current_stream().synchronize()      # the plane is complete before a record() reads it on the engine's stream
+
+    def _tile_order(self, plane):
+        """A tile-order copy of a plane in the current column order: follow() always starts from tile order."""
+        torch = self.torch
         if self.perm is None:
-            self.adjust_tile[name] = (plane, float(scale))
-        else:                                    # keep a tile-order copy: follow() always starts from tile order
-            inv = torch.empty_like(self.perm)
-            inv[self.perm.long()] = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
-            tile = torch.empty_like(plane)
-            torch.cuda.current_stream().synchronize()
-            self.engine.gather([tile], [plane], inv, self.ni, self.nj)()
-            self.engine.stream_sync()
-            self.adjust_tile[name] = (tile, float(scale))
+            return plane
+        inv = torch.empty_like(self.perm)
+        inv[self.perm.long()] = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
+        tile = torch.empty_like(plane)
+        torch.cuda.current_stream().synchronize()
+        self.engine.gather([tile], [plane], inv, self.ni, self.nj)()
+        self.engine.stream_sync()
+        return tile
+
+    MET_NAMES = ("t", "p", "q", "lw")
+
+    def set_elevation(self, z_model, z_source, lapse=-0.0065):
+        """From now on record() moves t, p, q and, if the record has it, lw from the source's terrain height to the model's
+        (noahmp_hip_forcing_regrid_met, in the same launch as the other names).  z_model: (nj, ni) device plane of the model's height in the
+        CURRENT column order; z_source: the source's height on its own grid.  dz = z_model - regrid_plane(z_source) is made once."""
+        torch = self.torch
+        if "t" in self.adjust:
+            raise ValueError("set_elevation and set_adjust('t', ...) exclude each other: the met group makes the lapse-rate correction itself")
+        z_model = z_model.to(torch.float32).contiguous()
+        assert z_model.numel() == self.ncell
+        self.dz = (z_model.reshape(self.nj, self.ni) - self.regrid_plane(z_source)).contiguous()
+        self.dz_tile = self._tile_order(self.dz)
+        self.lapse = float(lapse)
+        torch.cuda.current_stream().synchronize()      # dz is complete before a record() reads it on the engine's stream
 
     def record(self, planes, modes=None, stream=None):
         """{name: coarse device plane} -> {name: (nj, ni) device plane} in ONE launch, enqueued only on the engine's stream (or
@@ -69,6 +95,15 @@ class ForcingRegrid:
         the call (the engine's stream does not wait for torch's)."""
         torch = self.torch
         modes = modes or {}
+        met_names = ()
+        if self.dz is not None:
+            missing = [nm for nm in ("t", "p", "q") if planes.get(nm) is None]
+            if missing:
+                raise ValueError("with set_elevation a record needs t, p and q; missing: %s" % ", ".join(missing))
+            met_names = tuple(nm for nm in self.MET_NAMES if planes.get(nm) is not None)
+            for nm in met_names:
+                if modes.get(nm, "bilinear") != "bilinear":
+                    raise ValueError("with set_elevation %s is regridded bilinearly (mode %r asked)" % (nm, modes[nm]))
         out = self.sets[self.turn]
         self.turn ^= 1
         fresh = False
@@ -80,16 +115,24 @@ class ForcingRegrid:
             if name not in out:
                 out[name] = torch.empty((self.nj, self.ni), dtype=torch.float32, device=self.device)
                 fresh = True
+            if name in met_names:
+                continue
             adj, scale = self.adjust.get(name, (None, 0.0))
             entries.append((src, out[name], modes.get(name, "bilinear"), adj, scale, self.fill))
         if fresh:
             torch.cuda.current_stream().synchronize()
+        if met_names:
+            met = self.engine.regrid_met(planes["t"], planes["p"], planes["q"], out["t"], out["p"], out["q"], self.dz,
+                                         src_lw=planes.get("lw"), dst_lw=out.get("lw") if "lw" in met_names else None,
+                                         lapse=self.lapse, fill=self.fill)
+            self.engine.forcing_regrid_met(self.plan, self.ncell, self.source, met, entries[:32], stream=stream)
+            entries = entries[32:]
         for i in range(0, len(entries), 32):
             self.engine.forcing_regrid(self.plan, self.ncell, self.source, entries[i:i + 32], stream=stream)
         return {name: out[name] for name, src in planes.items() if src is not None}
 
     def follow(self, store):
-        """After Engine.sort_store(store): the six plan planes and the adjust planes, permuted into the store's column order with
+        """After Engine.sort_store(store): the six plan planes, the adjust planes and dz, permuted into the store's column order with
         noahmp_hip_gather_fields.  Waits for the engine's stream.  Records made before the call keep the old order."""
         torch = self.torch
         perm = getattr(store, "sort_perm", None)
@@ -99,13 +142,18 @@ class ForcingRegrid:
         new = torch.empty_like(self.plan_tile)
         names = list(self.adjust_tile)
         fresh = [torch.empty_like(self.adjust_tile[k][0]) for k in names]
+        new_dz = torch.empty_like(self.dz_tile) if self.dz_tile is not None else None
         torch.cuda.current_stream().synchronize()
         self.engine.stream_sync()
         dst = [new[k * n:(k + 1) * n] for k in range(6)] + fresh
         src = [self.plan_tile[k * n:(k + 1) * n] for k in range(6)] + [self.adjust_tile[k][0] for k in names]
+        if new_dz is not None:
+            dst.append(new_dz)
+            src.append(self.dz_tile)
         for i in range(0, len(dst), 32):
             self.engine.gather(dst[i:i + 32], src[i:i + 32], perm, self.ni, self.nj)()
         self.engine.stream_sync()
         self.plan, self.perm = new, perm
         self.adjust = {k: (t, self.adjust_tile[k][1]) for k, t in zip(names, fresh)}
+        self.dz = new_dz
         self.sets = [{}, {}]
