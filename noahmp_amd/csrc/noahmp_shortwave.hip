@@ -1,0 +1,172 @@
+// Shortwave forcing of a device-resident run (no reference counterpart: the reference interpolates SWDOWN linearly between two records,
+// netcdf_io:1369-1403; the contract is the text in include/noahmp_hip.h, the arithmetic is nmp_dev_shortwave.hpp).
+//
+// noahmp_hip_forcing_cosz_mean: once per forcing record.  One thread per column: latitude and longitude are read once, sin / cos of the
+// latitude made once, then the 1..64 sample suns -- which ride in the kernel arguments, 12 bytes each -- are walked from scalar registers.
+//
+// noahmp_hip_forcing_shortwave: ONE launch per step, after noahmp_hip_forcing_interpolate[_prep], whose linear SWDOWN it overwrites.  A pure
+// stream of 12 (LINEAR) to 36 bytes per column.  All loads of a column are issued before the first libm call; sinf_ / cosf_ hold no table,
+// so there is no LDS and no barrier.  One column per thread wherever a sun is made: see the note at the kernel.  Arguments go by value,
+// nothing is allocated, nothing waits on the host.
+#include <string.h>
+#include <hip/hip_runtime.h>
+#include "noahmp_hip.h"
+#include "nmp_dev_shortwave.hpp"
+#include "nmp_engine_host.hpp"
+
+using namespace nmp;
+using nmp_host::g;
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kMaxSamples = NOAHMP_SW_MAX_SAMPLES;
+
+struct MeanKArgs {                       // by value (< 1 KB)
+  const float* xlat; const float* lon;
+  float* mean;
+  long ncell;
+  int nsample;
+  SunTime t[kMaxSamples];
+};
+
+__global__ void __launch_bounds__(kBlock) noahmp_cosz_mean_kernel(const MeanKArgs k) {
+  const long c = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= k.ncell) return;
+  const float lat = k.xlat[c], lon = k.lon[c];
+  k.mean[c] = sun_interval_mean(lat, lon, k.nsample, k.t);
+}
+
+struct SwKArgs {
+  const float* sw_a; const float* sw_b; const float* mean_a;
+  const float* xlat; const float* lon;
+  const float* ne; const float* nn; const float* nu;
+  float* swdown;
+  long ncell;
+  SwParams p;
+};
+
+// VEC: NOAHMP_SW_LINEAR without normals -- no sun is made, the call is a pure stream of 8 or 12 bytes per column -- with sw_a, sw_b and
+// swdown 16-byte aligned and ncell a multiple of four: a thread owns four consecutive columns (16-byte loads and stores).  Every call
+// that makes a sun runs one column per thread whatever the alignment.  Registers would have allowed four there too (gfx950, the
+// compiler's own figures: one column 36 VGPRs, four columns 60, both without scratch and at 8 waves per SIMD), but the measurement did
+// not (tools/shortwave_bench.py with both forms built in, medians, 7 077 888 columns / the 884 736-column tile): ZENITH 0.0308 / 0.0088 ms
+// with four columns against 0.0337 / 0.0070 with one, ZENITH with terrain 0.0473 / 0.0117 against 0.0449 / 0.0089 -- four lose up to 31 %
+// on the tile, where a quarter of the threads no longer fills the chip, and win 9 % at most; LINEAR 0.0158 / 0.0044 against 0.0195 / 0.0044.
+template <bool VEC>
+__global__ void __launch_bounds__(kBlock) noahmp_shortwave_kernel(const SwKArgs k) {
+  constexpr int NC = VEC ? 4 : 1;
+  const long c = ((long)blockIdx.x * kBlock + threadIdx.x) * NC;
+  if (c >= k.ncell) return;
+  if constexpr (VEC) {
+    const float4 a = *(const float4*)(k.sw_a + c);
+    float4 o = a;
+    if (k.p.has_b) {
+      const float4 b = *(const float4*)(k.sw_b + c);
+      o.x = interp2(a.x, b.x, k.p.fraction, k.p.one_minus);
+      o.y = interp2(a.y, b.y, k.p.fraction, k.p.one_minus);
+      o.z = interp2(a.z, b.z, k.p.fraction, k.p.one_minus);
+      o.w = interp2(a.w, b.w, k.p.fraction, k.p.one_minus);
+    }
+    *(float4*)(k.swdown + c) = o;
+  } else {
+    const bool zenith = k.p.mode == NOAHMP_SW_ZENITH;
+    const bool sun = zenith || k.p.has_normal;
+    const float sw_a = k.sw_a[c];
+    float sw_b = 0.f, mean_a = 0.f, lat = 0.f, lon = 0.f, ne = 0.f, nn = 0.f, nu = 0.f;
+    if (k.p.has_b) sw_b = k.sw_b[c];
+    if (zenith) mean_a = k.mean_a[c];
+    if (sun) { lat = k.xlat[c]; lon = k.lon[c]; }
+    if (k.p.has_normal) { ne = k.ne[c]; nn = k.nn[c]; nu = k.nu[c]; }
+    __builtin_amdgcn_sched_barrier(0);   // the loads above are in flight before the first libm call
+    k.swdown[c] = sw_column(k.p, sw_a, sw_b, mean_a, lat, lon, ne, nn, nu);
+  }
+}
+
+inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }      // NULL counts as aligned: the plane is not read
+
+// what fill_forcing_args makes of a time (noahmp_forcing.hip): the declination with the host's libm, hour_utc left to right (hdrv:856)
+SunTime sun_of(const noahmp_sun_time& t) {
+  SunTime s;
+  noahmp_hip_declination(t.iday, t.ihour, &s.sin_declin, &s.cos_declin);
+  s.hour_utc = (float)t.ihour + (float)t.iminute / 60.0f + (float)t.isecond / 3600.0f;
+  return s;
+}
+
+int refuse(int rc, const char* who, const char* what) {
+  char b[240];
+  snprintf(b, sizeof b, "%s: %s", who, what);
+  g.last_error = b;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int noahmp_hip_forcing_cosz_mean(const float* xlat, const float* lon, int64_t ncell, int nsample, const noahmp_sun_time* times, float* mean,
+                                 void* stream) {
+  static const char* who = "noahmp_hip_forcing_cosz_mean";
+  if (nsample < 1 || nsample > kMaxSamples) {
+    char b[120];
+    snprintf(b, sizeof b, "1..%d samples per interval (nsample = %d)", kMaxSamples, nsample);
+    return refuse(-107, who, b);
+  }
+  if (!times) return refuse(-105, who, "times is NULL");
+  if (ncell < 0 || ncell > 0x7FFFFFFFL) return refuse(-105, who, "0 .. 2^31 - 1 columns");
+  if (!xlat || !lon || !mean) return refuse(-105, who, "xlat, lon and mean are required");
+  int rc = nmp_host::ensure_init();
+  if (rc) return rc;
+  if (ncell == 0) return 0;
+  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  MeanKArgs k;
+  memset(&k, 0, sizeof(k));
+  k.xlat = xlat; k.lon = lon; k.mean = mean; k.ncell = ncell; k.nsample = nsample;
+  for (int i = 0; i < nsample; i++) k.t[i] = sun_of(times[i]);
+  hipLaunchKernelGGL(noahmp_cosz_mean_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int noahmp_hip_forcing_shortwave(const noahmp_shortwave* sw, int64_t ncell, const noahmp_sun_time* now, void* stream) {
+  static const char* who = "noahmp_hip_forcing_shortwave";
+  if (!sw) return refuse(-105, who, "the argument block is NULL");
+  if (!now) return refuse(-105, who, "now is NULL");
+  if (sw->mode != NOAHMP_SW_LINEAR && sw->mode != NOAHMP_SW_ZENITH) {
+    char b[120];
+    snprintf(b, sizeof b, "mode %d (NOAHMP_SW_LINEAR, NOAHMP_SW_ZENITH)", sw->mode);
+    return refuse(-105, who, b);
+  }
+  if (ncell < 0 || ncell > 0x7FFFFFFFL) return refuse(-105, who, "0 .. 2^31 - 1 columns");
+  if (!sw->sw_a || !sw->xlat || !sw->lon || !sw->swdown) return refuse(-105, who, "sw_a, xlat, lon and swdown are required");
+  const bool zenith = sw->mode == NOAHMP_SW_ZENITH;
+  if (zenith && !sw->mean_a) return refuse(-105, who, "NOAHMP_SW_ZENITH needs mean_a (noahmp_hip_forcing_cosz_mean)");
+  const int nnormal = (sw->normal_e ? 1 : 0) + (sw->normal_n ? 1 : 0) + (sw->normal_u ? 1 : 0);
+  if (nnormal != 0 && nnormal != 3) return refuse(-105, who, "normal_e, normal_n and normal_u go together: all three or none");
+  const bool has_b = !zenith && sw->sw_b;
+  if (has_b && (sw->idts2 <= 0 || sw->idts < 0 || sw->idts > sw->idts2))
+    return refuse(-105, who, "target date outside the bracketing records (idts, idts2)");
+  int rc = nmp_host::ensure_init();
+  if (rc) return rc;
+  if (ncell == 0) return 0;
+  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  SwKArgs k;
+  memset(&k, 0, sizeof(k));
+  k.sw_a = sw->sw_a; k.sw_b = sw->sw_b; k.mean_a = sw->mean_a; k.xlat = sw->xlat; k.lon = sw->lon;
+  k.ne = sw->normal_e; k.nn = sw->normal_n; k.nu = sw->normal_u; k.swdown = sw->swdown; k.ncell = ncell;
+  k.p.now = sun_of(*now);
+  k.p.fraction = has_b ? (float)(sw->idts2 - sw->idts) / (float)sw->idts2 : 1.0f;      // netcdf_io:1390
+  k.p.one_minus = 1.0f - k.p.fraction;
+  k.p.max_ratio = sw->max_ratio; k.p.mu_min = sw->mu_min; k.p.max_terrain_ratio = sw->max_terrain_ratio;
+  k.p.solar_constant = sw->solar_constant;
+  k.p.mode = sw->mode; k.p.has_b = has_b ? 1 : 0; k.p.has_normal = nnormal == 3 ? 1 : 0;
+  const bool vec = !zenith && nnormal == 0 && (ncell & 3) == 0 && aligned16(k.sw_a) && aligned16(has_b ? k.sw_b : nullptr) && aligned16(k.swdown);
+  const long nthread = vec ? ncell / 4 : ncell;
+  const dim3 grid((unsigned)((nthread + kBlock - 1) / kBlock));
+  if (vec) hipLaunchKernelGGL(noahmp_shortwave_kernel<true>, grid, dim3(kBlock), 0, s, k);
+  else hipLaunchKernelGGL(noahmp_shortwave_kernel<false>, grid, dim3(kBlock), 0, s, k);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

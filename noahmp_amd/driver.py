@@ -610,6 +610,50 @@ class Engine:
         if rc:
             raise RuntimeError("noahmp_hip_forcing_regrid_met: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
+    # ---- shortwave forcing: zenith weighting in time, slope and aspect (noahmp_shortwave.hip; helper: noahmp_amd/shortwave.py)
+    @staticmethod
+    def sun_times(times):
+        """[(iday, ihour, iminute, isecond), ...] -> a prepared (SunTime * n) array."""
+        n = len(times)
+        arr = (abi.SunTime * max(n, 1))()
+        for i, (iday, ihour, iminute, isecond) in enumerate(times):
+            arr[i].iday, arr[i].ihour, arr[i].iminute, arr[i].isecond = int(iday), int(ihour), int(iminute), int(isecond)
+        arr._n = n
+        return arr
+
+    def cosz_mean(self, xlat, lon, times, mean, stream=None):
+        """mean <- the mean of max(cos zenith, 0) over `times` = [(iday, ihour, iminute, isecond), ...] (1..64 samples of a record's
+        interval) for every column of the float32 device planes xlat / lon: one kernel launch, enqueued only (noahmp_hip_forcing_cosz_mean)."""
+        if not isinstance(times, C.Array):
+            times = Engine.sun_times(times)
+        rc = self.lib.noahmp_hip_forcing_cosz_mean(xlat.data_ptr(), lon.data_ptr(), xlat.numel(), times._n, times, mean.data_ptr(), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_forcing_cosz_mean: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        return mean
+
+    @staticmethod
+    def shortwave_block(sw_a, xlat, lon, swdown, sw_b=None, mean_a=None, normal=None, idts=0, idts2=0, mode="zenith", max_ratio=10.0,
+                        mu_min=0.05, max_terrain_ratio=5.0, solar_constant=1361.0):
+        """A noahmp_shortwave block; normal = (east, north, up) planes or None.  The tensors are kept alive by the returned block."""
+        b = abi.Shortwave()
+        ne, nn, nu = normal if normal is not None else (None, None, None)
+        keep = dict(sw_a=sw_a, sw_b=sw_b, mean_a=mean_a, xlat=xlat, lon=lon, normal_e=ne, normal_n=nn, normal_u=nu, swdown=swdown)
+        for name, t in keep.items():
+            setattr(b, name, t.data_ptr() if t is not None else None)
+        b.idts, b.idts2 = int(idts), int(idts2)
+        b.mode = abi.SW_MODE[mode] if isinstance(mode, str) else int(mode)
+        b.max_ratio, b.mu_min, b.max_terrain_ratio, b.solar_constant = float(max_ratio), float(mu_min), float(max_terrain_ratio), float(solar_constant)
+        b._keep = keep
+        return b
+
+    def forcing_shortwave(self, block, ncell, now, stream=None):
+        """Downward shortwave of one step from a block of Engine.shortwave_block at now = (iday, ihour, iminute, isecond): one kernel
+        launch, enqueued only (noahmp_hip_forcing_shortwave).  Call it after forcing_interpolate[_prep], whose linear SWDOWN it overwrites."""
+        t = Engine.sun_times([now])
+        rc = self.lib.noahmp_hip_forcing_shortwave(C.byref(block), int(ncell), t, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_forcing_shortwave: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

@@ -1,0 +1,176 @@
+"""Downward shortwave of a device-resident run: weighted in time by the cosine of the solar zenith angle, moved to the sloping surface
+(noahmp_hip_forcing_cosz_mean / noahmp_hip_forcing_shortwave).
+
+    sw = Shortwave(engine, xlat, xlon, mode="zenith")            # (nj, ni) float32 device planes, degrees, TILE order
+    sw.set_terrain(slope, aspect)                                 # optional; or set_normal(e, n, u), or terrain_from_height(z, dx, dy)
+    sw.follow(store)                                              # after Engine.sort_store: lat, lon and the normals go into the store's order
+    mean_a = sw.interval((2000, 171, 18, 0, 0), 10800, 36)        # per record: mean of max(cos zenith, 0) over [a, b), 36 samples
+    engine.forcing_interpolate_prep(store, rec_a, rec_b, idts, idts2, rain, lon, iday, ihour, iminute, isecond, ...)
+    sw.apply(store, rec_a, rec_b, idts, idts2, (iday, ihour, iminute, isecond))      # per step: overwrites the store's linear SWDOWN
+
+The interpolation calls keep writing the reference's linear SWDOWN (netcdf_io:1369-1403); ``apply`` replaces it.  In mode "zenith" record
+a's value holds over [a, b) and is multiplied by cos(zenith now) / its interval mean, which keeps the interval's energy, follows the sun
+and writes exact zeros where the sun is down; mode "linear" keeps the reference's bits and only adds the terrain step.  The contract --
+every rounding -- is the text in include/noahmp_hip.h.
+"""
+import math
+
+
+def days_in_year(year):
+    return 366 if (year % 4 == 0 and (year % 100 != 0 or year % 400 == 0)) else 365
+
+
+def time_after(start, seconds):
+    """(year, iday, ihour, iminute, isecond) + whole seconds -> the same form; iday is the day of the year as noahmp_hip_forcing_prep takes
+    it (0 = 1 January) and rolls over into the next year."""
+    year, iday, ihour, iminute, isecond = (int(x) for x in start)
+    t = ((iday * 24 + ihour) * 60 + iminute) * 60 + isecond + int(seconds)
+    assert t >= 0, "a time before the start of the year"
+    iday, rest = divmod(t, 86400)
+    while iday >= days_in_year(year):
+        iday -= days_in_year(year)
+        year += 1
+    ihour, rest = divmod(rest, 3600)
+    iminute, isecond = divmod(rest, 60)
+    return year, iday, ihour, iminute, isecond
+
+
+def sample_times(start, seconds, nsample, at="start"):
+    """The nsample times of the interval [start, start + seconds): at="start" k * seconds / nsample (the step times of a model that makes
+    nsample steps per record, for which the zenith weighting conserves the record's energy exactly), at="mid" the midpoints; whole seconds."""
+    assert at in ("start", "mid") and nsample >= 1
+    if at == "start":
+        off = [k * int(seconds) // nsample for k in range(nsample)]
+    else:
+        off = [(2 * k + 1) * int(seconds) // (2 * nsample) for k in range(nsample)]
+    return [time_after(start, o) for o in off]
+
+
+def normal_from_height(z, dx, dy, cosalpha=None, sinalpha=None):
+    """The upward unit normal (east, north, up), the slope and the aspect [radians; downslope azimuth clockwise from true north] of a
+    terrain height z, an (nj, ni) torch plane, on a grid of spacing dx (along i) and dy (along j) [the unit of z]: central differences,
+    one-sided at the tile's edge.  cosalpha / sinalpha (WRF's COSALPHA / SINALPHA: the local rotation of the grid's y axis against true
+    north) turn the gradient from grid to earth coordinates."""
+    import torch
+    z = z.to(torch.float32)
+    gx, gy = torch.zeros_like(z), torch.zeros_like(z)
+    if z.shape[1] > 1:
+        gx[:, 1:-1] = (z[:, 2:] - z[:, :-2]) / (2.0 * dx)
+        gx[:, 0] = (z[:, 1] - z[:, 0]) / dx
+        gx[:, -1] = (z[:, -1] - z[:, -2]) / dx
+    if z.shape[0] > 1:
+        gy[1:-1, :] = (z[2:, :] - z[:-2, :]) / (2.0 * dy)
+        gy[0, :] = (z[1, :] - z[0, :]) / dy
+        gy[-1, :] = (z[-1, :] - z[-2, :]) / dy
+    if cosalpha is not None:                       # grid (x, y) -> earth (east, north), the rotation WRF applies to its winds
+        ge = gx * cosalpha - gy * sinalpha
+        gn = gx * sinalpha + gy * cosalpha
+    else:
+        ge, gn = gx, gy
+    g2 = ge * ge + gn * gn
+    norm = torch.sqrt(g2 + 1.0)
+    slope = torch.atan(torch.sqrt(g2))
+    aspect = torch.remainder(torch.atan2(-ge, -gn), 2.0 * math.pi)
+    return -ge / norm, -gn / norm, 1.0 / norm, slope, aspect      # the upward normal of z(x, y) is (-dz/dx, -dz/dy, 1) / |.|
+
+
+class Shortwave:
+    def __init__(self, engine, xlat, xlon, mode="zenith", max_ratio=10.0, mu_min=0.05, max_terrain_ratio=5.0, solar_constant=1361.0):
+        import torch
+        assert xlat.dtype == torch.float32 and xlon.dtype == torch.float32 and xlat.shape == xlon.shape and xlat.dim() == 2
+        assert mode in ("linear", "zenith")
+        self.engine, self.torch, self.mode = engine, torch, mode
+        self.nj, self.ni = xlat.shape
+        self.ncell = self.ni * self.nj
+        self.device = xlat.device
+        self.par = dict(max_ratio=max_ratio, mu_min=mu_min, max_terrain_ratio=max_terrain_ratio, solar_constant=solar_constant)
+        self.lat_tile, self.lon_tile = xlat.contiguous(), xlon.contiguous()
+        self.lat, self.lon = self.lat_tile, self.lon_tile          # in the column order the records are in
+        self.normal_tile = self.normal = None                        # (east, north, up) planes
+        self.perm = None
+        self.means = [None, None]                                    # two interval-mean planes, used alternately
+        self.turn = 0
+        self.mean_a = None                                           # the plane the last interval() filled
+        torch.cuda.current_stream().synchronize()
+
+    # ---- terrain
+    def set_normal(self, e, n, u):
+        """Unit surface normals in east / north / up components: (nj, ni) planes in the CURRENT column order."""
+        torch = self.torch
+        planes = tuple(t.to(torch.float32).contiguous() for t in (e, n, u))
+        assert all(t.numel() == self.ncell for t in planes)
+        self.normal = planes
+        self.normal_tile = tuple(self._tile_order(t) for t in planes)
+        torch.cuda.current_stream().synchronize()      # complete before an apply() reads them on the engine's stream
+
+    def set_terrain(self, slope, aspect):
+        """slope [radians] and aspect [radians, the downslope azimuth clockwise from true north]: the normal is
+        (sin s * sin a, sin s * cos a, cos s)."""
+        torch = self.torch
+        s, a = slope.to(torch.float32), aspect.to(torch.float32)
+        self.set_normal(torch.sin(s) * torch.sin(a), torch.sin(s) * torch.cos(a), torch.cos(s))
+
+    def terrain_from_height(self, z, dx, dy, cosalpha=None, sinalpha=None):
+        """set_normal(normal_from_height(...)) for the model's terrain height z, an (nj, ni) plane in TILE order.  Returns (slope, aspect)."""
+        assert self.perm is None, "terrain_from_height takes tile order: call it before follow(), follow() permutes the normals"
+        e, n, u, slope, aspect = normal_from_height(z, dx, dy, cosalpha, sinalpha)
+        self.set_normal(e, n, u)
+        return slope, aspect
+
+    def _tile_order(self, plane):
+        torch = self.torch
+        if self.perm is None:
+            return plane
+        inv = torch.empty_like(self.perm)
+        inv[self.perm.long()] = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
+        tile = torch.empty_like(plane)
+        torch.cuda.current_stream().synchronize()
+        self.engine.gather([tile], [plane], inv, self.ni, self.nj)()
+        self.engine.stream_sync()
+        return tile
+
+    def follow(self, store):
+        """After Engine.sort_store(store): lat, lon and the normals, permuted into the store's column order with noahmp_hip_gather_fields.
+        Waits for the engine's stream.  Interval means made before the call keep the old order: make them again."""
+        torch = self.torch
+        perm = getattr(store, "sort_perm", None)
+        assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
+        assert store.ni == self.ni and store.nj == self.nj
+        src = [self.lat_tile, self.lon_tile] + list(self.normal_tile or ())
+        dst = [torch.empty_like(t) for t in src]
+        torch.cuda.current_stream().synchronize()
+        self.engine.stream_sync()
+        self.engine.gather(dst, src, perm, self.ni, self.nj)()
+        self.engine.stream_sync()
+        self.lat, self.lon, self.perm = dst[0], dst[1], perm
+        self.normal = tuple(dst[2:]) if self.normal_tile is not None else None
+        self.means = [None, None]
+        self.mean_a = None
+
+    # ---- per record
+    def interval(self, start, seconds, nsample, at="start", stream=None):
+        """The mean of max(cos zenith, 0) over nsample times of [start, start + seconds), start = (year, iday, ihour, iminute, isecond):
+        one launch, enqueued only.  Returns the plane (and keeps it as mean_a for apply); two planes are used alternately."""
+        torch = self.torch
+        times = [t[1:] for t in sample_times(start, seconds, nsample, at)]
+        if self.means[self.turn] is None:
+            self.means[self.turn] = torch.empty((self.nj, self.ni), dtype=torch.float32, device=self.device)
+            torch.cuda.current_stream().synchronize()
+        out = self.means[self.turn]
+        self.turn ^= 1
+        self.engine.cosz_mean(self.lat, self.lon, times, out, stream=stream)
+        self.mean_a = out
+        return out
+
+    # ---- per step
+    def apply(self, store, rec_a, rec_b, idts, idts2, now, mean_a=None, stream=None):
+        """The store's SWDOWN at now = (iday, ihour, iminute, isecond) from the records' "sw" planes: one launch, enqueued only.  Call it
+        after forcing_interpolate[_prep] on the same stream.  rec_b may be None; it is read in mode "linear" only."""
+        mean_a = mean_a if mean_a is not None else self.mean_a
+        if self.mode == "zenith" and mean_a is None:
+            raise ValueError("mode 'zenith' needs the interval mean of record a: call interval() first")
+        sw_b = rec_b["sw"] if (rec_b is not None and self.mode == "linear") else None
+        block = self.engine.shortwave_block(rec_a["sw"], self.lat, self.lon, store.a["swdown"], sw_b=sw_b,
+                                            mean_a=mean_a if self.mode == "zenith" else None, normal=self.normal, idts=idts, idts2=idts2,
+                                            mode=self.mode, **self.par)
+        self.engine.forcing_shortwave(block, self.ncell, now, stream=stream)
