@@ -144,6 +144,7 @@ unsigned long long source_hash_public();
 void sort_finalize();     // noahmp_sort.hip
 void regions_finalize();  // noahmp_regions.hip
 void regrid_finalize();   // noahmp_regrid.hip
+void regrid_conserve_finalize();  // noahmp_regrid_conserve.hip
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
   char b_[256]; snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \

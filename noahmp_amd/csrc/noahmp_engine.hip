@@ -1175,6 +1175,7 @@ void noahmp_hip_finalize(void) {
   nmp_host::sort_finalize();
   nmp_host::regions_finalize();
   nmp_host::regrid_finalize();
+  nmp_host::regrid_conserve_finalize();
   for (auto& p : g.gw_mirror) { if (p) hipFree(p); p = nullptr; }
   for (auto& p : g.init_mirror) { if (p) hipFree(p); p = nullptr; }
   for (auto e : g.async_events) hipEventDestroy(e);

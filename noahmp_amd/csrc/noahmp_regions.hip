@@ -28,6 +28,7 @@
 #include <rocprim/rocprim.hpp>
 #include "noahmp_hip.h"
 #include "nmp_dev_regions.hpp"
+#include "nmp_region_tree.hpp"
 #include "nmp_engine_host.hpp"
 
 using namespace nmp;
@@ -35,11 +36,12 @@ using nmp_host::g;
 
 namespace {
 
-constexpr int kMaxEntries = NOAHMP_REG_MAX_ENTRIES, kChunk = NOAHMP_REG_CHUNK, kMaxLevels = 64;
-constexpr int kBlock = 256, kWaves = kBlock / 64;
+// the chunk / offset kernels and the fold of a chunk: nmp_region_tree.hpp (shared with noahmp_regrid_conserve.hip)
+using tree::kChunk; using tree::kBlock; using tree::kWaves;
+using tree::region_offsets_kernel; using tree::region_chunks_kernel; using tree::ChunkCount; using tree::wave_fold;
+constexpr int kMaxEntries = NOAHMP_REG_MAX_ENTRIES, kMaxLevels = 64;
 constexpr int kChunksPerWave = 4;        // consecutive chunks of one wave (level 1)
 constexpr int kBatch = 4;                // entries whose loads are issued before the first fold
-static_assert(kChunk == 256, "a wave of 64 lanes holds four elements of a chunk per lane");
 
 // the plan's header words
 enum { H_SPARE, H_NI, H_NJ, H_NREGION, H_NMEMBER, H_NCHUNK1, H_NCHUNK2, H_MAXC1, H_BAD, H_WEIGHT, H_WORDS = 16 };
@@ -89,33 +91,6 @@ __global__ void __launch_bounds__(kBlock) region_key_kernel(const int* region, l
   idx[t] = (int)t;
 }
 
-// roff[r] = first sorted cell whose key is >= r, r = 0 .. nregion (roff[nregion] = number of members)
-__global__ void __launch_bounds__(kBlock) region_offsets_kernel(const unsigned* keys, long n, int nregion, int* roff) {
-  const long r = (long)blockIdx.x * kBlock + threadIdx.x;
-  if (r > nregion) return;
-  long lo = 0, hi = n;
-  while (lo < hi) { const long mid = (lo + hi) >> 1; if (keys[mid] < (unsigned)r) lo = mid + 1; else hi = mid; }
-  roff[r] = (int)lo;
-}
-
-// chunks region i contributes to the next level: ceil(span / 256); the scan's input
-struct ChunkCount {
-  const int* off; int nregion;
-  __host__ __device__ int operator()(int i) const { return i < nregion ? (off[i + 1] - off[i] + kChunk - 1) / kChunk : 0; }
-};
-
-// cstart[c] = first element of chunk c, c = 0 .. total; chunk c ends at min(cstart[c] + 256, cstart[c+1]) (regions are adjacent)
-__global__ void __launch_bounds__(kBlock) region_chunks_kernel(const int* off, const int* choff, int nregion, long bound, int* cstart, int* hdr_max) {
-  const long c = (long)blockIdx.x * kBlock + threadIdx.x;
-  const int total = choff[nregion];
-  if (c > total || c > bound) return;
-  if (c == total) { cstart[c] = off[nregion]; return; }
-  int lo = 0, hi = nregion;              // the last region whose first chunk is <= c: it is not empty
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (choff[mid] <= (int)c) lo = mid; else hi = mid - 1; }
-  cstart[c] = off[lo] + kChunk * ((int)c - choff[lo]);
-  if (hdr_max && (int)c == choff[lo]) atomicMax(hdr_max, choff[lo + 1] - choff[lo]);      // integer: the widest region of this level
-}
-
 // weights and positions in member order; weight NULL: positions only (noahmp_hip_region_plan_follow)
 __global__ void __launch_bounds__(kBlock) region_members_kernel(const int* tile, const int* roff, int nregion, const float* weight, bool set_w,
                                                                 const int* inv_perm, float* w, int* pos) {
@@ -132,15 +107,6 @@ __global__ void region_header_kernel(int* hdr, const int* roff, const int* choff
 }
 
 // ---------------------------------------------------------------------------------------------------------------- step kernels
-// one chunk in a wave: lane l holds elements l, l+64, l+128, l+192.  v[i] = v[i] + v[i+h] for i < h, h = 128 .. 1; lane 0 has the result.
-__device__ __forceinline__ double wave_fold(int op, double v0, double v1, double v2, double v3) {
-  v0 = reg_combine(op, v0, v2); v1 = reg_combine(op, v1, v3);       // h = 128
-  v0 = reg_combine(op, v0, v1);                                     // h = 64
-#pragma unroll
-  for (int h = 32; h > 0; h >>= 1) v0 = reg_combine(op, v0, __shfl_down(v0, h, 64));
-  return v0;
-}
-
 struct L1Args {                          // by value
   const float* src[kMaxEntries];
   int nlev[kMaxEntries], lev[kMaxEntries], op[kMaxEntries];

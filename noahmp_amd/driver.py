@@ -610,6 +610,78 @@ class Engine:
         if rc:
             raise RuntimeError("noahmp_hip_forcing_regrid_met: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
+    # ---- budget-preserving regrid of fluxes (noahmp_regrid_conserve.hip; helper: noahmp_amd/regrid.py)
+    class RegridConservePlan:
+        """The device workspace noahmp_hip_regrid_conserve_plan filled, the regrid plan it was made from, and what a record on it needs."""
+
+        def __init__(self, cplan, regrid_plan, ni, nj, source, clipped):
+            self.cplan, self.regrid_plan, self.ni, self.nj, self.source, self.clipped = cplan, regrid_plan, ni, nj, source, clipped
+            self.scratch = None
+
+    def regrid_conserve_plan(self, regrid_plan, ni, nj, source, area=None, dst_index=None, domain_edges=0b1111, stream=None):
+        """Conserve plan of a window (noahmp_hip_regrid_conserve_plan) from its regrid plan in WINDOW order: area = float32 device tensor
+        in window order or None (= 1); dst_index = int32 device tensor in window order (negative: a margin cell, summed but not written) or
+        None (identity); domain_edges = NOAHMP_REGRID_EDGE_* bits of the window's sides that are edges of the whole model domain.
+        Returns a RegridConservePlan; .clipped > 0: widen the margin.  Built on the device; waits."""
+        import torch
+        assert regrid_plan.dtype == torch.int32 and regrid_plan.numel() >= 6 * ni * nj
+        assert area is None or (area.dtype == torch.float32 and area.is_contiguous() and area.numel() == ni * nj)
+        assert dst_index is None or (dst_index.dtype == torch.int32 and dst_index.is_contiguous() and dst_index.numel() == ni * nj)
+        words = C.c_int64(0)
+        rc = self.lib.noahmp_hip_regrid_conserve_plan_size(ni, nj, C.byref(source), C.byref(words))
+        if rc:
+            raise RuntimeError("noahmp_hip_regrid_conserve_plan_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        cplan = torch.empty((words.value + 1) // 2, dtype=torch.int64, device=regrid_plan.device).view(torch.int32)
+        torch.cuda.current_stream().synchronize()
+        clipped = C.c_int32(0)
+        rc = self.lib.noahmp_hip_regrid_conserve_plan(regrid_plan.data_ptr(), ni, nj, C.byref(source), area.data_ptr() if area is not None else None,
+                                                      dst_index.data_ptr() if dst_index is not None else None, int(domain_edges),
+                                                      cplan.data_ptr(), cplan.numel(), C.byref(clipped), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_regrid_conserve_plan: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        return Engine.RegridConservePlan(cplan, regrid_plan, ni, nj, source, int(clipped.value))
+
+    @staticmethod
+    def regrid_conserve_entries(entries):
+        """[(src tensor, dst tensor, pattern tensor or None, fill), ...] -> a prepared (RegridConserveEntry * n) array.  The tensors are
+        kept alive by the returned array."""
+        n = len(entries)
+        arr = (abi.RegridConserveEntry * max(n, 1))()
+        for f, (src, dst, pattern, fill) in enumerate(entries):
+            arr[f].src = src.data_ptr() if src is not None else None
+            arr[f].dst = dst.data_ptr() if dst is not None else None
+            arr[f].pattern = pattern.data_ptr() if pattern is not None else None
+            arr[f].fill = float(fill)
+        arr._n, arr._keep = n, list(entries)
+        arr._ndst = min([e[1].numel() for e in entries if e[1] is not None] or [0])
+        return arr
+
+    def regrid_conserve_scratch_bytes(self, cp, n):
+        b = C.c_int64(0)
+        rc = self.lib.noahmp_hip_regrid_conserve_scratch_size(cp.cplan.data_ptr(), n, C.byref(b))
+        if rc:
+            raise RuntimeError("noahmp_hip_regrid_conserve_scratch_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        return int(b.value)
+
+    def forcing_regrid_conserve(self, cp, entries, dst_index=None, group_sum=None, stream=None):
+        """1..8 entries through a RegridConservePlan (noahmp_hip_forcing_regrid_conserve): at most four launches, enqueued only; the scratch
+        is allocated at the first call on a plan.  dst_index: int32 device tensor in window order (the positions of the window cells in the
+        destination planes; negative = not written) or None; group_sum: float64 device tensor over the source grid that receives N_s of
+        entry 0, or None."""
+        import torch
+        if not isinstance(entries, C.Array):
+            entries = Engine.regrid_conserve_entries(entries)
+        need = self.regrid_conserve_scratch_bytes(cp, entries._n)
+        if cp.scratch is None or cp.scratch.numel() * 8 < need:
+            cp.scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=cp.cplan.device)
+            torch.cuda.current_stream().synchronize()
+        rc = self.lib.noahmp_hip_forcing_regrid_conserve(cp.cplan.data_ptr(), cp.regrid_plan.data_ptr(), C.byref(cp.source),
+                                                         dst_index.data_ptr() if dst_index is not None else None, int(entries._ndst),
+                                                         entries._n, entries, group_sum.data_ptr() if group_sum is not None else None,
+                                                         cp.scratch.data_ptr(), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_forcing_regrid_conserve: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     # ---- shortwave forcing: zenith weighting in time, slope and aspect (noahmp_shortwave.hip; helper: noahmp_amd/shortwave.py)
     @staticmethod
     def sun_times(times):

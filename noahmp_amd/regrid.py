@@ -4,7 +4,9 @@
     rg = ForcingRegrid(engine, xlat, xlon, src, valid=None, search_radius=4)      # builds the plan; rg.unfilled
     rg.set_adjust("t", z_model - rg.regrid_plane(z_source), scale=-0.0065)       # optional: lapse-rate correction of one plane, or
     rg.set_elevation(z_model, z_source, lapse=-0.0065)                           # optional: t, p, q, lw moved to the model's terrain height
-    rec = rg.record({"t": t_c, "q": q_c, ..., "pcp": p_c}, modes={"pcp": "nearest"})
+    rg.set_conserve(area=cell_area)                                              # optional: budget-preserving regrid of fluxes; rg.clipped
+    rg.set_pattern("pcp", prism_ratio)                                           # optional: a fine climatology pattern of one conserve plane
+    rec = rg.record({"t": t_c, "q": q_c, ..., "pcp": p_c}, modes={"pcp": "conserve"})      # or "nearest" / "bilinear"
     rg.follow(store)          # after Engine.sort_store: plan and adjust planes go into the store's column order
 
 ``record()`` returns what ``Engine.forcing_interpolate[_prep]`` takes as ``rec_a`` / ``rec_b``: a dict of (nj, ni) device planes.  Two
@@ -32,6 +34,11 @@ class ForcingRegrid:
         self.turn = 0
         self.dz_tile = self.dz = None            # set_elevation: model height - regridded source height, tile order / current order
         self.lapse = 0.0
+        self.valid, self.search_radius = valid, search_radius
+        self.conserve = None                     # set_conserve: the Engine.RegridConservePlan of the window
+        self.clipped = 0                         # groups the window cuts (set_conserve); > 0: widen the margin
+        self.window_tile = self.dst_index = None # per window cell: its tile index or -1 / its position in the current column order or -1
+        self.patterns = {}                       # name -> plane in window order
 
     def _check_source_plane(self, t, name):
         assert t.dtype == self.torch.float32 and t.is_contiguous() and t.numel() == self.source.nx * self.source.ny, \
@@ -89,10 +96,64 @@ class ForcingRegrid:
         self.lapse = float(lapse)
         torch.cuda.current_stream().synchronize()      # dz is complete before a record() reads it on the engine's stream
 
+    def set_conserve(self, area=None, window=None, domain_edges=0b1111):
+        """From now on record() serves the names whose mode is "conserve" with noahmp_hip_forcing_regrid_conserve: bilinear, optionally
+        shaped by a pattern, rescaled so that the area-weighted mean over the model cells of each source cell is the source cell's value.
+        area: float32 device plane of the window's shape in WINDOW order (TILE order without a window), or None = 1.  window =
+        (xlat_w, xlon_w, i0, j0): a wider rectangle of model cells that holds the tile at column i0, row j0 -- the margin of a
+        decomposed run, wide enough to hold every model cell of every source cell that owns a tile cell; None: the tile itself.
+        domain_edges: NOAHMP_REGRID_EDGE_* bits of the window's sides that are edges of the whole model domain.  Sets rg.clipped: the
+        number of source cells that own a tile cell and reach a side of the window that is no domain edge; > 0: widen the margin.  Waits."""
+        torch = self.torch
+        if window is None:
+            plan_w, nj_w, ni_w, i0, j0 = self.plan_tile, self.nj, self.ni, 0, 0
+        else:
+            xlat_w, xlon_w, i0, j0 = window
+            nj_w, ni_w = xlat_w.shape
+            assert 0 <= i0 and i0 + self.ni <= ni_w and 0 <= j0 and j0 + self.nj <= nj_w, "the window must hold the tile"
+            plan_w, _ = self.engine.regrid_plan(xlat_w.contiguous(), xlon_w.contiguous(), self.source, valid=self.valid, search_radius=self.search_radius)
+        tile = torch.full((nj_w, ni_w), -1, dtype=torch.int32, device=self.device)
+        tile[j0:j0 + self.nj, i0:i0 + self.ni] = torch.arange(self.ncell, dtype=torch.int32, device=self.device).reshape(self.nj, self.ni)
+        self.window_tile = tile.contiguous()
+        if area is not None:
+            area = area.to(torch.float32).contiguous()
+            assert area.numel() == nj_w * ni_w, "area has the window's shape"
+        self._refresh_dst_index()
+        torch.cuda.current_stream().synchronize()
+        self.conserve = self.engine.regrid_conserve_plan(plan_w, ni_w, nj_w, self.source, area=area, dst_index=self.dst_index, domain_edges=domain_edges)
+        self.clipped = self.conserve.clipped
+        self.patterns = {}
+
+    def _refresh_dst_index(self):
+        """dst_index of the window cells for the current column order: only this changes after a re-sort."""
+        torch = self.torch
+        if self.perm is None:
+            self.dst_index = self.window_tile
+            return
+        inv = torch.empty_like(self.perm)
+        inv[self.perm.long()] = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
+        t = self.window_tile
+        self.dst_index = torch.where(t >= 0, inv[t.clamp(min=0).long()], t).to(torch.int32).contiguous()
+
+    def set_pattern(self, name, plane):
+        """Conserve plane `name` is shaped by `plane` before it is rescaled (a fine climatology, PRISM-style): a float32 device plane of
+        the window's shape in WINDOW order; None removes it."""
+        torch = self.torch
+        assert self.conserve is not None, "set_pattern follows set_conserve"
+        if plane is None:
+            self.patterns.pop(name, None)
+            return
+        plane = plane.to(torch.float32).contiguous()
+        assert plane.numel() == self.conserve.ni * self.conserve.nj, "a pattern has the window's shape"
+        self.patterns[name] = plane
+        torch.cuda.current_stream().synchronize()
+
     def record(self, planes, modes=None, stream=None):
         """{name: coarse device plane} -> {name: (nj, ni) device plane} in ONE launch, enqueued only on the engine's stream (or
-        `stream`); modes: {name: "bilinear" | "nearest"}, default bilinear.  The coarse planes must be complete on the device before
-        the call (the engine's stream does not wait for torch's)."""
+        `stream`); modes: {name: "bilinear" | "nearest" | "conserve"}, default bilinear.  The names in mode "conserve" (after
+        set_conserve) go through noahmp_hip_forcing_regrid_conserve, at most four more launches per eight names; everything else through
+        the one launch, unchanged.  The coarse planes must be complete on the device before the call (the engine's stream does not wait
+        for torch's)."""
         torch = self.torch
         modes = modes or {}
         met_names = ()
@@ -107,7 +168,7 @@ class ForcingRegrid:
         out = self.sets[self.turn]
         self.turn ^= 1
         fresh = False
-        entries = []
+        entries, conserve = [], []
         for name, src in planes.items():
             if src is None:
                 continue
@@ -116,6 +177,13 @@ class ForcingRegrid:
                 out[name] = torch.empty((self.nj, self.ni), dtype=torch.float32, device=self.device)
                 fresh = True
             if name in met_names:
+                continue
+            if modes.get(name) == "conserve":
+                if self.conserve is None:
+                    raise ValueError("mode 'conserve' (%s) needs set_conserve first" % name)
+                if name in self.adjust:
+                    raise ValueError("%s: a conserve plane takes no adjust" % name)
+                conserve.append((src, out[name], self.patterns.get(name), self.fill))
                 continue
             adj, scale = self.adjust.get(name, (None, 0.0))
             entries.append((src, out[name], modes.get(name, "bilinear"), adj, scale, self.fill))
@@ -129,11 +197,14 @@ class ForcingRegrid:
             entries = entries[32:]
         for i in range(0, len(entries), 32):
             self.engine.forcing_regrid(self.plan, self.ncell, self.source, entries[i:i + 32], stream=stream)
+        for i in range(0, len(conserve), 8):
+            self.engine.forcing_regrid_conserve(self.conserve, conserve[i:i + 8], dst_index=self.dst_index, stream=stream)
         return {name: out[name] for name, src in planes.items() if src is not None}
 
     def follow(self, store):
         """After Engine.sort_store(store): the six plan planes, the adjust planes and dz, permuted into the store's column order with
-        noahmp_hip_gather_fields.  Waits for the engine's stream.  Records made before the call keep the old order."""
+        noahmp_hip_gather_fields; the conserve plan keeps its window order and only dst_index is made anew.  Waits for the engine's stream.
+        Records made before the call keep the old order."""
         torch = self.torch
         perm = getattr(store, "sort_perm", None)
         assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
@@ -157,3 +228,6 @@ class ForcingRegrid:
         self.adjust = {k: (t, self.adjust_tile[k][1]) for k, t in zip(names, fresh)}
         self.dz = new_dz
         self.sets = [{}, {}]
+        if self.conserve is not None:            # the conserve plan stays as it is: only the positions of the window cells change
+            self._refresh_dst_index()
+            torch.cuda.current_stream().synchronize()
