@@ -121,7 +121,8 @@ NMP_DEV float sw_zenith(float sw_a, float mean, float mu, float max_ratio) {
 }
 
 // slope and aspect: s on the horizontal -> the flux per unit map area on the surface with unit normal (ne, nn, nu); the form of WRF's
-// topo_rad_adj.  Self-shading through cosi <= 0; no cast shadows, no terrain-reflected light.
+// topo_rad_adj.  Self-shading through cosi <= 0; cast shadows come in through sw_column_lit (the plane of nmp_dev_shadow.hpp) only; no
+// terrain-reflected light.
 NMP_DEV float sw_terrain(float s, const SunVec& v, float mu, float ne, float nn, float nu, float mu_min, float max_terrain_ratio,
                          float solar_constant) {
 #if defined(__clang__)
@@ -172,6 +173,52 @@ NMP_DEV float sw_column(const SwParams& k, float sw_a, float sw_b, float mean_a,
   else s = k.has_b ? interp2(sw_a, sw_b, k.fraction, k.one_minus) : sw_a;
   if (k.has_normal) s = sw_terrain(s, v, mu, ne, nn, nu, k.mu_min, k.max_terrain_ratio, k.solar_constant);
   return s;
+}
+
+// one column of noahmp_hip_forcing_shortwave_lit.  lit == 1.0f gives the bits of sw_column: the same functions on the same operands in
+// the same order, and r0*1.0f is r0; every other value (a cast shadow, a fraction, a NaN) scales the direct beam, with or without
+// normals.  One body for both, so that a wave with lit and shadowed lanes runs the sun, the time stage and the Erbs fraction once, not
+// once per kind of lane (the first form called sw_column for the lit lanes: 1.41 of the unshaded call at mu ~ 0.10 with 13 % of the
+// columns in shadow, tools/shadow_bench.py).
+NMP_DEV float sw_column_lit(const SwParams& k, float lit, float sw_a, float sw_b, float mean_a, float lat, float lon, float ne, float nn,
+                            float nu) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const bool zenith = k.mode == NOAHMP_SW_ZENITH;
+  const bool shaded = !(lit == 1.0f);                          // a NaN is shaded
+  if (!shaded && !zenith && !k.has_normal) return k.has_b ? interp2(sw_a, sw_b, k.fraction, k.one_minus) : sw_a;      // sw_column makes no sun here
+  const float phi = lat * NMP_DEGRAD;
+  const float sinphi = libm::sinf_(phi), cosphi = libm::cosf_(phi);
+  const float hrang = sun_hrang(lon, k.now.hour_utc);
+  SunVec v;
+  v.e = v.n = 0.f;
+  if (k.has_normal) v = sun_vector(sinphi, cosphi, hrang, k.now.sin_declin, k.now.cos_declin);
+  else v.u = sun_up(sinphi, cosphi, hrang, k.now.sin_declin, k.now.cos_declin);
+  const float mu = sw_max0(v.u);
+  float s;
+  if (zenith) s = sw_zenith(sw_a, mean_a, mu, k.max_ratio);
+  else s = k.has_b ? interp2(sw_a, sw_b, k.fraction, k.one_minus) : sw_a;
+  const bool sloped = k.has_normal && !(ne == 0.f && nn == 0.f);
+  if (!shaded && !sloped) return s;                            // no normals, or flat: the bits of s, as sw_column / sw_terrain
+  if (mu < k.mu_min) return s;                                 // sun low or down: the bits of s
+  float r0 = 1.0f;
+  if (sloped) {                                                // the lines of sw_terrain
+    const float pe = v.e * ne;
+    const float pn = v.n * nn;
+    const float pu = v.u * nu;
+    const float pen = pe + pn;
+    const float cosi = pen + pu;
+    r0 = sw_min(sw_max0(cosi) / mu, k.max_terrain_ratio);
+  }
+  const float top = k.solar_constant * mu;
+  const float kt = s / top;
+  const float kd = sw_erbs_kd(kt);
+  const float r = r0 * lit;                                    // lit == 1.0f: the bits of r0
+  const float beam = 1.0f - kd;
+  const float br = beam * r;
+  const float f = kd + br;
+  return s * f;
 }
 
 }  // namespace nmp

@@ -8,6 +8,9 @@
 // stream of 12 (LINEAR) to 36 bytes per column.  All loads of a column are issued before the first libm call; sinf_ / cosf_ hold no table,
 // so there is no LDS and no barrier.  One column per thread wherever a sun is made: see the note at the kernel.  Arguments go by value,
 // nothing is allocated, nothing waits on the host.
+//
+// noahmp_hip_forcing_shortwave_lit: the same step with the lit plane of noahmp_hip_forcing_shadow (noahmp_shadow.hip) on the direct beam;
+// a kernel of its own, so the call above keeps its kernels and its bits.
 #include <string.h>
 #include <hip/hip_runtime.h>
 #include "noahmp_hip.h"
@@ -83,6 +86,23 @@ __global__ void __launch_bounds__(kBlock) noahmp_shortwave_kernel(const SwKArgs 
   }
 }
 
+// noahmp_hip_forcing_shortwave_lit: the one-column form above plus the 4 bytes of the lit plane; a sun may be needed in every column
+// (a shadowed one scales its beam whatever the mode), so latitude and longitude are always loaded.
+__global__ void __launch_bounds__(kBlock) noahmp_shortwave_lit_kernel(const SwKArgs k, const float* __restrict__ lit_plane) {
+  const long c = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= k.ncell) return;
+  const bool zenith = k.p.mode == NOAHMP_SW_ZENITH;
+  const float lit = lit_plane[c];
+  const float sw_a = k.sw_a[c];
+  const float lat = k.xlat[c], lon = k.lon[c];
+  float sw_b = 0.f, mean_a = 0.f, ne = 0.f, nn = 0.f, nu = 0.f;
+  if (k.p.has_b) sw_b = k.sw_b[c];
+  if (zenith) mean_a = k.mean_a[c];
+  if (k.p.has_normal) { ne = k.ne[c]; nn = k.nn[c]; nu = k.nu[c]; }
+  __builtin_amdgcn_sched_barrier(0);   // the loads above are in flight before the first libm call
+  k.swdown[c] = sw_column_lit(k.p, lit, sw_a, sw_b, mean_a, lat, lon, ne, nn, nu);
+}
+
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }      // NULL counts as aligned: the plane is not read
 
 // what fill_forcing_args makes of a time (noahmp_forcing.hip): the declination with the host's libm, hour_utc left to right (hdrv:856)
@@ -98,6 +118,39 @@ int refuse(int rc, const char* who, const char* what) {
   snprintf(b, sizeof b, "%s: %s", who, what);
   g.last_error = b;
   return rc;
+}
+
+// the checks of both shortwave calls and their kernel arguments; 0, or the refusal
+int sw_prepare(const char* who, const noahmp_shortwave* sw, int64_t ncell, const noahmp_sun_time* now, SwKArgs* out) {
+  if (!sw) return refuse(-105, who, "the argument block is NULL");
+  if (!now) return refuse(-105, who, "now is NULL");
+  if (sw->mode != NOAHMP_SW_LINEAR && sw->mode != NOAHMP_SW_ZENITH) {
+    char b[120];
+    snprintf(b, sizeof b, "mode %d (NOAHMP_SW_LINEAR, NOAHMP_SW_ZENITH)", sw->mode);
+    return refuse(-105, who, b);
+  }
+  if (ncell < 0 || ncell > 0x7FFFFFFFL) return refuse(-105, who, "0 .. 2^31 - 1 columns");
+  if (!sw->sw_a || !sw->xlat || !sw->lon || !sw->swdown) return refuse(-105, who, "sw_a, xlat, lon and swdown are required");
+  const bool zenith = sw->mode == NOAHMP_SW_ZENITH;
+  if (zenith && !sw->mean_a) return refuse(-105, who, "NOAHMP_SW_ZENITH needs mean_a (noahmp_hip_forcing_cosz_mean)");
+  const int nnormal = (sw->normal_e ? 1 : 0) + (sw->normal_n ? 1 : 0) + (sw->normal_u ? 1 : 0);
+  if (nnormal != 0 && nnormal != 3) return refuse(-105, who, "normal_e, normal_n and normal_u go together: all three or none");
+  const bool has_b = !zenith && sw->sw_b;
+  if (has_b && (sw->idts2 <= 0 || sw->idts < 0 || sw->idts > sw->idts2))
+    return refuse(-105, who, "target date outside the bracketing records (idts, idts2)");
+  int rc = nmp_host::ensure_init();
+  if (rc) return rc;
+  SwKArgs& k = *out;
+  memset(&k, 0, sizeof(k));
+  k.sw_a = sw->sw_a; k.sw_b = sw->sw_b; k.mean_a = sw->mean_a; k.xlat = sw->xlat; k.lon = sw->lon;
+  k.ne = sw->normal_e; k.nn = sw->normal_n; k.nu = sw->normal_u; k.swdown = sw->swdown; k.ncell = ncell;
+  k.p.now = sun_of(*now);
+  k.p.fraction = has_b ? (float)(sw->idts2 - sw->idts) / (float)sw->idts2 : 1.0f;      // netcdf_io:1390
+  k.p.one_minus = 1.0f - k.p.fraction;
+  k.p.max_ratio = sw->max_ratio; k.p.mu_min = sw->mu_min; k.p.max_terrain_ratio = sw->max_terrain_ratio;
+  k.p.solar_constant = sw->solar_constant;
+  k.p.mode = sw->mode; k.p.has_b = has_b ? 1 : 0; k.p.has_normal = nnormal == 3 ? 1 : 0;
+  return 0;
 }
 
 }  // namespace
@@ -130,41 +183,30 @@ int noahmp_hip_forcing_cosz_mean(const float* xlat, const float* lon, int64_t nc
 
 int noahmp_hip_forcing_shortwave(const noahmp_shortwave* sw, int64_t ncell, const noahmp_sun_time* now, void* stream) {
   static const char* who = "noahmp_hip_forcing_shortwave";
-  if (!sw) return refuse(-105, who, "the argument block is NULL");
-  if (!now) return refuse(-105, who, "now is NULL");
-  if (sw->mode != NOAHMP_SW_LINEAR && sw->mode != NOAHMP_SW_ZENITH) {
-    char b[120];
-    snprintf(b, sizeof b, "mode %d (NOAHMP_SW_LINEAR, NOAHMP_SW_ZENITH)", sw->mode);
-    return refuse(-105, who, b);
-  }
-  if (ncell < 0 || ncell > 0x7FFFFFFFL) return refuse(-105, who, "0 .. 2^31 - 1 columns");
-  if (!sw->sw_a || !sw->xlat || !sw->lon || !sw->swdown) return refuse(-105, who, "sw_a, xlat, lon and swdown are required");
-  const bool zenith = sw->mode == NOAHMP_SW_ZENITH;
-  if (zenith && !sw->mean_a) return refuse(-105, who, "NOAHMP_SW_ZENITH needs mean_a (noahmp_hip_forcing_cosz_mean)");
-  const int nnormal = (sw->normal_e ? 1 : 0) + (sw->normal_n ? 1 : 0) + (sw->normal_u ? 1 : 0);
-  if (nnormal != 0 && nnormal != 3) return refuse(-105, who, "normal_e, normal_n and normal_u go together: all three or none");
-  const bool has_b = !zenith && sw->sw_b;
-  if (has_b && (sw->idts2 <= 0 || sw->idts < 0 || sw->idts > sw->idts2))
-    return refuse(-105, who, "target date outside the bracketing records (idts, idts2)");
-  int rc = nmp_host::ensure_init();
+  SwKArgs k;
+  int rc = sw_prepare(who, sw, ncell, now, &k);
   if (rc) return rc;
   if (ncell == 0) return 0;
   hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
-  SwKArgs k;
-  memset(&k, 0, sizeof(k));
-  k.sw_a = sw->sw_a; k.sw_b = sw->sw_b; k.mean_a = sw->mean_a; k.xlat = sw->xlat; k.lon = sw->lon;
-  k.ne = sw->normal_e; k.nn = sw->normal_n; k.nu = sw->normal_u; k.swdown = sw->swdown; k.ncell = ncell;
-  k.p.now = sun_of(*now);
-  k.p.fraction = has_b ? (float)(sw->idts2 - sw->idts) / (float)sw->idts2 : 1.0f;      // netcdf_io:1390
-  k.p.one_minus = 1.0f - k.p.fraction;
-  k.p.max_ratio = sw->max_ratio; k.p.mu_min = sw->mu_min; k.p.max_terrain_ratio = sw->max_terrain_ratio;
-  k.p.solar_constant = sw->solar_constant;
-  k.p.mode = sw->mode; k.p.has_b = has_b ? 1 : 0; k.p.has_normal = nnormal == 3 ? 1 : 0;
-  const bool vec = !zenith && nnormal == 0 && (ncell & 3) == 0 && aligned16(k.sw_a) && aligned16(has_b ? k.sw_b : nullptr) && aligned16(k.swdown);
+  const bool zenith = k.p.mode == NOAHMP_SW_ZENITH;
+  const bool vec = !zenith && !k.p.has_normal && (ncell & 3) == 0 && aligned16(k.sw_a) && aligned16(k.p.has_b ? k.sw_b : nullptr) && aligned16(k.swdown);
   const long nthread = vec ? ncell / 4 : ncell;
   const dim3 grid((unsigned)((nthread + kBlock - 1) / kBlock));
   if (vec) hipLaunchKernelGGL(noahmp_shortwave_kernel<true>, grid, dim3(kBlock), 0, s, k);
   else hipLaunchKernelGGL(noahmp_shortwave_kernel<false>, grid, dim3(kBlock), 0, s, k);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int noahmp_hip_forcing_shortwave_lit(const noahmp_shortwave* sw, const float* lit, int64_t ncell, const noahmp_sun_time* now, void* stream) {
+  static const char* who = "noahmp_hip_forcing_shortwave_lit";
+  if (!lit) return refuse(-105, who, "lit is NULL (noahmp_hip_forcing_shadow makes it)");
+  SwKArgs k;
+  int rc = sw_prepare(who, sw, ncell, now, &k);
+  if (rc) return rc;
+  if (ncell == 0) return 0;
+  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipLaunchKernelGGL(noahmp_shortwave_lit_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k, lit);
   HIPCHK(hipGetLastError());
   return 0;
 }

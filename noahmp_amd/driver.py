@@ -726,6 +726,41 @@ class Engine:
         if rc:
             raise RuntimeError("noahmp_hip_forcing_shortwave: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
+    # ---- cast shadows: terrain ray march and the lit shortwave step (noahmp_shadow.hip, noahmp_shortwave.hip; helper: noahmp_amd/shortwave.py)
+    @staticmethod
+    def shadow_block(height, xlat, lon, lit, dx, dy, nstep=25, cosalpha=None, sinalpha=None, dst_index=None, mu_min=0.05, height_max=None):
+        """A noahmp_shadow block over the (nj, ni) WINDOW planes height / xlat / lon (float32, device): lit = the destination plane,
+        dst_index = int32 plane in window order (negative: a margin cell, read but neither marched nor written) or None (identity).
+        height_max defaults to the window's maximum (one device-to-host copy; a decomposed run must pass the GLOBAL maximum, the same
+        number on every rank).  The tensors are kept alive by the returned block."""
+        assert height.dim() == 2 and height.is_contiguous() and xlat.numel() == height.numel() and lon.numel() == height.numel()
+        b = abi.Shadow()
+        keep = dict(height=height, xlat=xlat, lon=lon, cosalpha=cosalpha, sinalpha=sinalpha, dst_index=dst_index, lit=lit)
+        for name, t in keep.items():
+            setattr(b, name, t.data_ptr() if t is not None else None)
+        b.nj, b.ni = (int(v) for v in height.shape)
+        b.nstep = int(nstep)
+        b.dx, b.dy, b.mu_min = float(dx), float(dy), float(mu_min)
+        b.height_max = float(height_max) if height_max is not None else (float(height.max().item()) if height.numel() else 0.0)
+        b._keep = keep
+        return b
+
+    def forcing_shadow(self, block, ndst, now, stream=None):
+        """The lit plane of a block of Engine.shadow_block at now = (iday, ihour, iminute, isecond): 1.0 where the cell sees the sun, 0.0
+        in a cast shadow.  One kernel launch, enqueued only (noahmp_hip_forcing_shadow)."""
+        t = Engine.sun_times([now])
+        rc = self.lib.noahmp_hip_forcing_shadow(C.byref(block), int(ndst), t, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_forcing_shadow: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
+    def forcing_shortwave_lit(self, block, lit, ncell, now, stream=None):
+        """forcing_shortwave with the lit plane (ncell floats, the column order of the block's planes) on the direct beam: one kernel
+        launch, enqueued only (noahmp_hip_forcing_shortwave_lit)."""
+        t = Engine.sun_times([now])
+        rc = self.lib.noahmp_hip_forcing_shortwave_lit(C.byref(block), lit.data_ptr() if lit is not None else None, int(ncell), t, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_forcing_shortwave_lit: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

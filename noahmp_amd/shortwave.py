@@ -3,6 +3,7 @@
 
     sw = Shortwave(engine, xlat, xlon, mode="zenith")            # (nj, ni) float32 device planes, degrees, TILE order
     sw.set_terrain(slope, aspect)                                 # optional; or set_normal(e, n, u), or terrain_from_height(z, dx, dy)
+    sw.set_shadow(height, dx, dy, nstep=25)                        # optional: cast shadows by a ray march over the terrain (window = tile + margin)
     sw.follow(store)                                              # after Engine.sort_store: lat, lon and the normals go into the store's order
     mean_a = sw.interval((2000, 171, 18, 0, 0), 10800, 36)        # per record: mean of max(cos zenith, 0) over [a, b), 36 samples
     engine.forcing_interpolate_prep(store, rec_a, rec_b, idts, idts2, rain, lon, iday, ihour, iminute, isecond, ...)
@@ -91,6 +92,9 @@ class Shortwave:
         self.means = [None, None]                                    # two interval-mean planes, used alternately
         self.turn = 0
         self.mean_a = None                                           # the plane the last interval() filled
+        self.shadow = None                                           # set_shadow: the window planes and the noahmp_shadow block
+        self.lit = None                                              # the lit plane, in the column order the records are in
+        self.shadow_calls = 0
         torch.cuda.current_stream().synchronize()
 
     # ---- terrain
@@ -116,6 +120,56 @@ class Shortwave:
         e, n, u, slope, aspect = normal_from_height(z, dx, dy, cosalpha, sinalpha)
         self.set_normal(e, n, u)
         return slope, aspect
+
+    # ---- cast shadows
+    def set_shadow(self, height, dx, dy, nstep=25, origin=(0, 0), cosalpha=None, sinalpha=None, height_max=None, every=1):
+        """Cast shadows on the direct beam (noahmp_hip_forcing_shadow + noahmp_hip_forcing_shortwave_lit).  height: the terrain height
+        [m] of an (nj_w, ni_w) WINDOW that contains the tile with its cell (0, 0) at window cell origin = (i0, j0); the cells around the
+        tile are the margin that lets a ray cross the tile's edge: at least nstep cells on every side that is not an edge of the whole
+        domain give the bits of the undecomposed run.  dx, dy: grid spacing [m]; nstep: cells marched (25 at 1 km = WRF's shadlen);
+        cosalpha / sinalpha: WRF's rotation planes over the window, or None (grid y is true north).  height_max defaults to the
+        WINDOW's maximum: a decomposed run must pass the GLOBAL maximum, the same number on every rank, or ranks disagree on where a
+        ray is above all terrain.  every: the lit plane is made again at every `every`-th apply() and reused in between (the sun moves
+        0.25 degrees per minute).  apply() then enqueues the shadow launch and the lit shortwave call in place of the unshaded one;
+        terrain normals are optional.  Works before or after follow()."""
+        torch = self.torch
+        assert height.dim() == 2 and (cosalpha is None) == (sinalpha is None) and int(every) >= 1
+        i0, j0 = (int(v) for v in origin)
+        nj_w, ni_w = height.shape
+        assert 0 <= i0 and i0 + self.ni <= ni_w and 0 <= j0 and j0 + self.nj <= nj_w, "the window must contain the tile at origin"
+        h = height.to(torch.float32).contiguous()
+        lat, lon = torch.zeros_like(h), torch.zeros_like(h)      # only tile cells are marched, so only they need a sun
+        lat[j0:j0 + self.nj, i0:i0 + self.ni] = self.lat_tile
+        lon[j0:j0 + self.nj, i0:i0 + self.ni] = self.lon_tile
+        rot = None
+        if cosalpha is not None:
+            rot = tuple(t.to(torch.float32).contiguous() for t in (cosalpha, sinalpha))
+            assert all(t.shape == h.shape for t in rot)
+        hmax = float(height_max) if height_max is not None else float(h.max().item())
+        self.shadow = dict(height=h, lat=lat, lon=lon, rot=rot, dx=float(dx), dy=float(dy), nstep=int(nstep), origin=(i0, j0), height_max=hmax,
+                           every=int(every))
+        self.lit = torch.empty((self.nj, self.ni), dtype=torch.float32, device=self.device)
+        self.shadow_calls = 0
+        self._shadow_index()
+
+    def _shadow_index(self):
+        """dst_index of the shadow window: the position of every tile cell in the current column order, -1 in the margin."""
+        torch = self.torch
+        sh = self.shadow
+        i0, j0 = sh["origin"]
+        if self.perm is None:
+            pos = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
+        else:
+            pos = torch.empty(self.ncell, dtype=torch.int32, device=self.device)
+            pos[self.perm.long()] = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
+        index = torch.full(sh["height"].shape, -1, dtype=torch.int32, device=self.device)
+        index[j0:j0 + self.nj, i0:i0 + self.ni] = pos.reshape(self.nj, self.ni)
+        rot = sh["rot"] or (None, None)
+        sh["index"] = index.contiguous()
+        sh["block"] = self.engine.shadow_block(sh["height"], sh["lat"], sh["lon"], self.lit, sh["dx"], sh["dy"], nstep=sh["nstep"], cosalpha=rot[0],
+                                               sinalpha=rot[1], dst_index=sh["index"], mu_min=self.par["mu_min"], height_max=sh["height_max"])
+        self.shadow_calls = 0
+        torch.cuda.current_stream().synchronize()      # complete before an apply() reads them on the engine's stream
 
     def _tile_order(self, plane):
         torch = self.torch
@@ -146,6 +200,8 @@ class Shortwave:
         self.normal = tuple(dst[2:]) if self.normal_tile is not None else None
         self.means = [None, None]
         self.mean_a = None
+        if self.shadow is not None:
+            self._shadow_index()
 
     # ---- per record
     def interval(self, start, seconds, nsample, at="start", stream=None):
@@ -173,4 +229,10 @@ class Shortwave:
         block = self.engine.shortwave_block(rec_a["sw"], self.lat, self.lon, store.a["swdown"], sw_b=sw_b,
                                             mean_a=mean_a if self.mode == "zenith" else None, normal=self.normal, idts=idts, idts2=idts2,
                                             mode=self.mode, **self.par)
-        self.engine.forcing_shortwave(block, self.ncell, now, stream=stream)
+        if self.shadow is None:
+            self.engine.forcing_shortwave(block, self.ncell, now, stream=stream)
+            return
+        if self.shadow_calls % self.shadow["every"] == 0:
+            self.engine.forcing_shadow(self.shadow["block"], self.ncell, now, stream=stream)
+        self.shadow_calls += 1
+        self.engine.forcing_shortwave_lit(block, self.lit, self.ncell, now, stream=stream)
