@@ -13,7 +13,8 @@ LIB = os.path.join(CSRC, "libnoahmp_hip.so")
 SOURCES = ["noahmp_engine.hip", "noahmp_groundwater.hip", "noahmp_init.hip", "noahmp_forcing.hip", "noahmp_engine_d1_r1.hip",
            "noahmp_engine_d3_r1.hip", "noahmp_engine_d3_r5.hip", "noahmp_engine_d4_r1.hip", "noahmp_engine_d4_r3.hip",
            "noahmp_jit.hip", "noahmp_sort.hip", "noahmp_halo.hip", "noahmp_stage.hip", "noahmp_history.hip", "noahmp_regions.hip",
-           "noahmp_regrid.hip", "noahmp_shortwave.hip", "noahmp_regrid_conserve.hip", "noahmp_shadow.hip"]
+           "noahmp_regrid.hip", "noahmp_shortwave.hip", "noahmp_regrid_conserve.hip", "noahmp_shadow.hip",
+           "noahmp_skyview.hip"]
 
 
 def _headers():

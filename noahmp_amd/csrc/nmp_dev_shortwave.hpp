@@ -221,4 +221,81 @@ NMP_DEV float sw_column_lit(const SwParams& k, float lit, float sw_a, float sw_b
   return s * f;
 }
 
+// one column of noahmp_hip_forcing_radiation_sky, the shortwave: svf == 1.0f gives the bits of sw_column_lit, all its shortcuts included,
+// and albedo is not looked at; every other value (a NaN included) narrows the diffuse part to the visible sky and adds the light the
+// closed part reflects, for which the column's own horizontal global flux stands in for that of the surrounding slopes.  One body for both
+// kinds of lane, for the reason given at sw_column_lit.
+NMP_DEV float sw_column_sky(const SwParams& k, float svf, float lit, float albedo, float sw_a, float sw_b, float mean_a, float lat, float lon,
+                            float ne, float nn, float nu) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const bool zenith = k.mode == NOAHMP_SW_ZENITH;
+  const bool open = svf == 1.0f;                               // a NaN is not open
+  const bool shaded = !(lit == 1.0f);
+  if (open && !shaded && !zenith && !k.has_normal) return k.has_b ? interp2(sw_a, sw_b, k.fraction, k.one_minus) : sw_a;
+  const float phi = lat * NMP_DEGRAD;
+  const float sinphi = libm::sinf_(phi), cosphi = libm::cosf_(phi);
+  const float hrang = sun_hrang(lon, k.now.hour_utc);
+  SunVec v;
+  v.e = v.n = 0.f;
+  if (k.has_normal) v = sun_vector(sinphi, cosphi, hrang, k.now.sin_declin, k.now.cos_declin);
+  else v.u = sun_up(sinphi, cosphi, hrang, k.now.sin_declin, k.now.cos_declin);
+  const float mu = sw_max0(v.u);
+  float s;
+  if (zenith) s = sw_zenith(sw_a, mean_a, mu, k.max_ratio);
+  else s = k.has_b ? interp2(sw_a, sw_b, k.fraction, k.one_minus) : sw_a;
+  const bool sloped = k.has_normal && !(ne == 0.f && nn == 0.f);
+  const bool low = mu < k.mu_min;
+  if (open && ((!shaded && !sloped) || low)) return s;         // the shortcuts of sw_column_lit: the bits of s
+  float r = 1.0f, kd = 0.f;
+  if (!low) {
+    float r0 = 1.0f;
+    if (sloped) {                                              // the lines of sw_terrain
+      const float pe = v.e * ne;
+      const float pn = v.n * nn;
+      const float pu = v.u * nu;
+      const float pen = pe + pn;
+      const float cosi = pen + pu;
+      r0 = sw_min(sw_max0(cosi) / mu, k.max_terrain_ratio);
+    }
+    const float top = k.solar_constant * mu;
+    const float kt = s / top;
+    kd = sw_erbs_kd(kt);
+    r = r0 * lit;
+  }
+  const float beam = 1.0f - kd;
+  const float br = beam * r;
+  if (open) {                                                  // not low here: the last lines of sw_column_lit
+    const float f = kd + br;
+    return s * f;
+  }
+  float f0 = svf;                                              // sun low or down: whatever s holds is diffuse
+  if (!low) {
+    const float dif = kd * svf;
+    f0 = dif + br;
+  }
+  const float o = 1.0f - svf;
+  const float refl = albedo * o;
+  const float f = f0 + refl;
+  return s * f;
+}
+
+// one column of noahmp_hip_forcing_radiation_sky, the longwave: the visible sky's share of g plus what the closed part of the hemisphere
+// emits at the column's own surface temperature and emissivity; svf == 1.0f keeps the bits of g
+NMP_DEV float lw_column_sky(float svf, float g, float tsurf, float emiss, float sigma) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (svf == 1.0f) return g;
+  const float o = 1.0f - svf;
+  const float t2 = tsurf * tsurf;
+  const float t4 = t2 * t2;
+  const float b = sigma * t4;
+  const float eb = emiss * b;
+  const float up = o * eb;
+  const float dn = svf * g;
+  return dn + up;
+}
+
 }  // namespace nmp

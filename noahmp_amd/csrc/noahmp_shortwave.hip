@@ -11,6 +11,9 @@
 //
 // noahmp_hip_forcing_shortwave_lit: the same step with the lit plane of noahmp_hip_forcing_shadow (noahmp_shadow.hip) on the direct beam;
 // a kernel of its own, so the call above keeps its kernels and its bits.
+//
+// noahmp_hip_forcing_radiation_sky: the lit step plus the sky-view terms of the shortwave plus the longwave of the closed part of the
+// hemisphere, in ONE launch -- again a kernel of its own.  The sky-view plane is that of noahmp_hip_skyview (noahmp_skyview.hip).
 #include <string.h>
 #include <hip/hip_runtime.h>
 #include "noahmp_hip.h"
@@ -101,6 +104,38 @@ __global__ void __launch_bounds__(kBlock) noahmp_shortwave_lit_kernel(const SwKA
   if (k.p.has_normal) { ne = k.ne[c]; nn = k.nn[c]; nu = k.nu[c]; }
   __builtin_amdgcn_sched_barrier(0);   // the loads above are in flight before the first libm call
   k.swdown[c] = sw_column_lit(k.p, lit, sw_a, sw_b, mean_a, lat, lon, ne, nn, nu);
+}
+
+// noahmp_hip_forcing_radiation_sky: the lit form plus 4 bytes of sky view, up to 8 of lit and albedo, and the longwave group (GLW in and
+// out, surface temperature, up to 4 of emissivity).  Every load of the column is issued before the first libm call; the longwave itself
+// holds no libm.  A column with an open sky (svf == 1.0f) keeps its GLW without a store.
+struct SkyKArgs {
+  const float* svf; const float* lit; const float* albedo; const float* tsurf; const float* emiss;
+  float* glw;
+  float albedo_const, emiss_const, sigma;
+};
+
+__global__ void __launch_bounds__(kBlock) noahmp_radiation_sky_kernel(const SwKArgs k, const SkyKArgs y) {
+  const long c = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= k.ncell) return;
+  const bool zenith = k.p.mode == NOAHMP_SW_ZENITH;
+  const float svf = y.svf[c];
+  const float sw_a = k.sw_a[c];
+  const float lat = k.xlat[c], lon = k.lon[c];
+  float lit = 1.0f, albedo = y.albedo_const, emiss = y.emiss_const, g = 0.f, tsurf = 0.f;
+  float sw_b = 0.f, mean_a = 0.f, ne = 0.f, nn = 0.f, nu = 0.f;
+  if (y.lit) lit = y.lit[c];
+  if (y.albedo) albedo = y.albedo[c];
+  if (k.p.has_b) sw_b = k.sw_b[c];
+  if (zenith) mean_a = k.mean_a[c];
+  if (k.p.has_normal) { ne = k.ne[c]; nn = k.nn[c]; nu = k.nu[c]; }
+  if (y.glw) {
+    g = y.glw[c]; tsurf = y.tsurf[c];
+    if (y.emiss) emiss = y.emiss[c];
+  }
+  __builtin_amdgcn_sched_barrier(0);   // the loads above are in flight before the first libm call
+  k.swdown[c] = sw_column_sky(k.p, svf, lit, albedo, sw_a, sw_b, mean_a, lat, lon, ne, nn, nu);
+  if (y.glw && !(svf == 1.0f)) y.glw[c] = lw_column_sky(svf, g, tsurf, emiss, y.sigma);
 }
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }      // NULL counts as aligned: the plane is not read
@@ -207,6 +242,25 @@ int noahmp_hip_forcing_shortwave_lit(const noahmp_shortwave* sw, const float* li
   if (ncell == 0) return 0;
   hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
   hipLaunchKernelGGL(noahmp_shortwave_lit_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k, lit);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int noahmp_hip_forcing_radiation_sky(const noahmp_shortwave* sw, const noahmp_sky* sky, int64_t ncell, const noahmp_sun_time* now, void* stream) {
+  static const char* who = "noahmp_hip_forcing_radiation_sky";
+  if (!sky) return refuse(-105, who, "the sky block is NULL");
+  if (!sky->svf) return refuse(-105, who, "svf is NULL (noahmp_hip_skyview makes it)");
+  if (sky->glw && !sky->tsurf) return refuse(-105, who, "glw needs tsurf");
+  SwKArgs k;
+  int rc = sw_prepare(who, sw, ncell, now, &k);
+  if (rc) return rc;
+  if (ncell == 0) return 0;
+  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  SkyKArgs y;
+  memset(&y, 0, sizeof(y));
+  y.svf = sky->svf; y.lit = sky->lit; y.albedo = sky->albedo; y.glw = sky->glw; y.tsurf = sky->tsurf; y.emiss = sky->emiss;
+  y.albedo_const = sky->albedo_const; y.emiss_const = sky->emiss_const; y.sigma = sky->sigma;
+  hipLaunchKernelGGL(noahmp_radiation_sky_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k, y);
   HIPCHK(hipGetLastError());
   return 0;
 }

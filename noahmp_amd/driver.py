@@ -761,6 +761,69 @@ class Engine:
         if rc:
             raise RuntimeError("noahmp_hip_forcing_shortwave_lit: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
+    # ---- sky-view factor: horizon scan and the radiation step with it (noahmp_skyview.hip, noahmp_shortwave.hip; helper: noahmp_amd/shortwave.py)
+    @staticmethod
+    def skyview_directions(ndir):
+        """The direction table of the horizon scan: (float32) sin / cos (2 pi q / ndir), q = 0 .. ndir-1, made in float64."""
+        import numpy as np
+        a = 2.0 * np.pi * np.arange(int(ndir), dtype=np.float64) / int(ndir)
+        return np.sin(a).astype(np.float32), np.cos(a).astype(np.float32)
+
+    @staticmethod
+    def skyview_block(height, svf, dx, dy, nstep=25, ndir=16, dst_index=None, dir_x=None, dir_y=None):
+        """A noahmp_skyview block over the (nj, ni) WINDOW plane height (float32, device): svf = the destination plane, dst_index = int32
+        plane in window order (negative: a margin cell, read but neither scanned nor written) or None (identity).  dir_x / dir_y: host
+        float32 arrays in grid coordinates; by default Engine.skyview_directions(ndir).  Tensors and arrays are kept alive by the block."""
+        import numpy as np
+        assert height.dim() == 2 and height.is_contiguous()
+        if dir_x is None:
+            dir_x, dir_y = Engine.skyview_directions(ndir)
+        dir_x, dir_y = (np.ascontiguousarray(v, np.float32) for v in (dir_x, dir_y))
+        assert dir_x.size == dir_y.size
+        b = abi.Skyview()
+        keep = dict(height=height, dst_index=dst_index, svf=svf)
+        for name, t in keep.items():
+            setattr(b, name, t.data_ptr() if t is not None else None)
+        b.dir_x, b.dir_y = dir_x.ctypes.data, dir_y.ctypes.data
+        b.nj, b.ni = (int(v) for v in height.shape)
+        b.nstep, b.ndir = int(nstep), int(dir_x.size)
+        b.dx, b.dy = float(dx), float(dy)
+        b._keep = dict(keep, dir_x=dir_x, dir_y=dir_y)
+        return b
+
+    def skyview(self, block, ndst, stream=None):
+        """The sky-view factor of a block of Engine.skyview_block: 1.0 where a horizontal receiver sees the whole hemisphere.  One kernel
+        launch, enqueued only, once per terrain (noahmp_hip_skyview)."""
+        rc = self.lib.noahmp_hip_skyview(C.byref(block), int(ndst), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_skyview: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
+    @staticmethod
+    def sky_block(svf, lit=None, albedo=0.2, glw=None, tsurf=None, emiss=0.95, sigma=5.67e-8):
+        """A noahmp_sky block: svf / lit / glw / tsurf are float32 device planes or None; albedo and emiss a plane or the constant of every
+        column.  The tensors are kept alive by the returned block."""
+        b = abi.Sky()
+        planes = dict(svf=svf, lit=lit, glw=glw, tsurf=tsurf, albedo=None, emiss=None)
+        b.albedo_const = b.emiss_const = 0.0
+        for name, v in (("albedo", albedo), ("emiss", emiss)):
+            if hasattr(v, "data_ptr"):
+                planes[name] = v
+            else:
+                setattr(b, name + "_const", float(v))
+        for name, t in planes.items():
+            setattr(b, name, t.data_ptr() if t is not None else None)
+        b.sigma = float(sigma)
+        b._keep = planes
+        return b
+
+    def forcing_radiation_sky(self, block, sky, ncell, now, stream=None):
+        """forcing_shortwave_lit plus the sky-view terms of the shortwave and the longwave of the closed part of the hemisphere, from a block
+        of Engine.shortwave_block and one of Engine.sky_block: one kernel launch, enqueued only (noahmp_hip_forcing_radiation_sky)."""
+        t = Engine.sun_times([now])
+        rc = self.lib.noahmp_hip_forcing_radiation_sky(C.byref(block), C.byref(sky), int(ncell), t, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_forcing_radiation_sky: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

@@ -4,6 +4,7 @@
     sw = Shortwave(engine, xlat, xlon, mode="zenith")            # (nj, ni) float32 device planes, degrees, TILE order
     sw.set_terrain(slope, aspect)                                 # optional; or set_normal(e, n, u), or terrain_from_height(z, dx, dy)
     sw.set_shadow(height, dx, dy, nstep=25)                        # optional: cast shadows by a ray march over the terrain (window = tile + margin)
+    sw.set_skyview(height, dx, dy, nstep=25, ndir=16)              # optional: sky-view factor by a horizon scan (the same window), once
     sw.follow(store)                                              # after Engine.sort_store: lat, lon and the normals go into the store's order
     mean_a = sw.interval((2000, 171, 18, 0, 0), 10800, 36)        # per record: mean of max(cos zenith, 0) over [a, b), 36 samples
     engine.forcing_interpolate_prep(store, rec_a, rec_b, idts, idts2, rain, lon, iday, ihour, iminute, isecond, ...)
@@ -95,6 +96,8 @@ class Shortwave:
         self.shadow = None                                           # set_shadow: the window planes and the noahmp_shadow block
         self.lit = None                                              # the lit plane, in the column order the records are in
         self.shadow_calls = 0
+        self.sky = None                                              # set_skyview: the sources of the per-step planes and the constants
+        self.svf_tile = self.svf = None                              # the sky-view plane in tile order / the column order the records are in
         torch.cuda.current_stream().synchronize()
 
     # ---- terrain
@@ -171,6 +174,50 @@ class Shortwave:
         self.shadow_calls = 0
         torch.cuda.current_stream().synchronize()      # complete before an apply() reads them on the engine's stream
 
+    # ---- sky-view factor
+    def set_skyview(self, height, dx, dy, nstep=25, ndir=16, origin=(0, 0), albedo="store", longwave=True, emiss="store", tsurf="tsk",
+                    sigma=5.67e-8):
+        """Sky-view factor in the radiation (noahmp_hip_skyview + noahmp_hip_forcing_radiation_sky).  height, dx, dy, origin: the WINDOW of
+        set_shadow (a caller that uses both passes the same window); a margin of at least nstep cells on every side that is not an edge of
+        the whole domain gives the bits of the undecomposed run.  The terrain is scanned ONCE, here, along ndir directions (grid
+        coordinates, (float32) sin / cos (2 pi q / ndir)) for nstep cells each, into a tile-order plane that is kept; follow() permutes it.
+        apply() then enqueues the shadow launch as before (if set_shadow was called) and the radiation call in place of the shortwave
+        call: the diffuse shortwave is narrowed to the visible sky, the closed part of the hemisphere reflects with `albedo`, and -- with
+        longwave=True -- the store's GLW becomes svf*GLW + (1 - svf)*emiss*sigma*tsurf^4.  albedo / emiss: "store" = the plane of that name
+        of the store passed to apply(), or a float = the constant of every column; tsurf: the name of the store's temperature plane.
+        ALBEDO and EMISS are OUTPUTS of the step: before the first step the caller gives constants here or initialised planes in the
+        store.  Works before or after follow()."""
+        torch = self.torch
+        assert height.dim() == 2
+        i0, j0 = (int(v) for v in origin)
+        nj_w, ni_w = height.shape
+        assert 0 <= i0 and i0 + self.ni <= ni_w and 0 <= j0 and j0 + self.nj <= nj_w, "the window must contain the tile at origin"
+        h = height.to(torch.float32).contiguous()
+        index = torch.full(h.shape, -1, dtype=torch.int32, device=self.device)
+        index[j0:j0 + self.nj, i0:i0 + self.ni] = torch.arange(self.ncell, dtype=torch.int32, device=self.device).reshape(self.nj, self.ni)
+        index = index.contiguous()
+        self.svf_tile = torch.empty((self.nj, self.ni), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream().synchronize()
+        self.engine.skyview(self.engine.skyview_block(h, self.svf_tile, dx, dy, nstep=nstep, ndir=ndir, dst_index=index), self.ncell)
+        self.engine.stream_sync()
+        self.sky = dict(albedo=albedo, emiss=emiss, tsurf=tsurf, longwave=bool(longwave), sigma=float(sigma))
+        self.svf = self.svf_tile
+        if self.perm is not None:
+            self.svf = torch.empty_like(self.svf_tile)
+            torch.cuda.current_stream().synchronize()
+            self.engine.gather([self.svf], [self.svf_tile], self.perm, self.ni, self.nj)()
+            self.engine.stream_sync()
+
+    def _sky_block(self, store):
+        sky = self.sky
+        plane = lambda v: store.a[v] if isinstance(v, str) else v      # noqa: E731  "store" names the plane of the store, a float is the constant
+        albedo = plane("albedo" if sky["albedo"] == "store" else sky["albedo"])
+        emiss = plane("emiss" if sky["emiss"] == "store" else sky["emiss"])
+        glw = store.a["glw"] if sky["longwave"] else None
+        tsurf = store.a[sky["tsurf"]] if sky["longwave"] else None
+        return self.engine.sky_block(self.svf, lit=self.lit if self.shadow is not None else None, albedo=albedo, glw=glw, tsurf=tsurf,
+                                     emiss=emiss, sigma=sky["sigma"])
+
     def _tile_order(self, plane):
         torch = self.torch
         if self.perm is None:
@@ -190,14 +237,16 @@ class Shortwave:
         perm = getattr(store, "sort_perm", None)
         assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
         assert store.ni == self.ni and store.nj == self.nj
-        src = [self.lat_tile, self.lon_tile] + list(self.normal_tile or ())
+        src = [self.lat_tile, self.lon_tile] + list(self.normal_tile or ()) + ([self.svf_tile] if self.svf_tile is not None else [])
         dst = [torch.empty_like(t) for t in src]
         torch.cuda.current_stream().synchronize()
         self.engine.stream_sync()
         self.engine.gather(dst, src, perm, self.ni, self.nj)()
         self.engine.stream_sync()
         self.lat, self.lon, self.perm = dst[0], dst[1], perm
-        self.normal = tuple(dst[2:]) if self.normal_tile is not None else None
+        self.normal = tuple(dst[2:5]) if self.normal_tile is not None else None
+        if self.svf_tile is not None:
+            self.svf = dst[-1]
         self.means = [None, None]
         self.mean_a = None
         if self.shadow is not None:
@@ -229,10 +278,14 @@ class Shortwave:
         block = self.engine.shortwave_block(rec_a["sw"], self.lat, self.lon, store.a["swdown"], sw_b=sw_b,
                                             mean_a=mean_a if self.mode == "zenith" else None, normal=self.normal, idts=idts, idts2=idts2,
                                             mode=self.mode, **self.par)
-        if self.shadow is None:
+        if self.shadow is None and self.sky is None:
             self.engine.forcing_shortwave(block, self.ncell, now, stream=stream)
             return
-        if self.shadow_calls % self.shadow["every"] == 0:
-            self.engine.forcing_shadow(self.shadow["block"], self.ncell, now, stream=stream)
-        self.shadow_calls += 1
-        self.engine.forcing_shortwave_lit(block, self.lit, self.ncell, now, stream=stream)
+        if self.shadow is not None:
+            if self.shadow_calls % self.shadow["every"] == 0:
+                self.engine.forcing_shadow(self.shadow["block"], self.ncell, now, stream=stream)
+            self.shadow_calls += 1
+        if self.sky is None:
+            self.engine.forcing_shortwave_lit(block, self.lit, self.ncell, now, stream=stream)
+        else:
+            self.engine.forcing_radiation_sky(block, self._sky_block(store), self.ncell, now, stream=stream)
