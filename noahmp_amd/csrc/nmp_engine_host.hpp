@@ -55,6 +55,7 @@ struct Engine {
   std::vector<float> sync_step_ms;            // noahmp_hip_sync_step_timing: land (or mixed) kernel of each step of the last sync
   std::vector<signed char> async_kind;              // per pending step: launch_any's kind (0 one kernel, 1 class kernels in a row, 2 forked)
   int last_launch_kind = 0;
+  int last_host_path = 0;       // set_option("last_host_path"): 1 single-shot staging, 2 row-chunk pipeline, 3 resident (tile-order mirrors), 4 resident on the sorted mirror set
   // "record_cost": per-column trip counts of the last device-resident step, in the tile's current column order (Ctx::cost)
   unsigned char* d_cost = nullptr; size_t d_cost_bytes = 0; long cost_cols = 0; int record_cost = 0;
   bool cost_fresh = false;                    // written by a step since the last permutation of the state
@@ -151,6 +152,12 @@ void regrid_conserve_finalize();  // noahmp_regrid_conserve.hip
   nmp_host::g.last_error = b_; return -100; } } while (0)
 
 int ensure_init();
+// Index-block validation of every entry point that takes a noahmp_step_args (rules: the header text of the struct).  0, or -103 with
+// g.last_error = "<who>: index block refused, <bound>: ...".  Needs no device: call it before ensure_init().
+constexpr int kNeedStepLevels = 1;   // kts and kts + 1 inside kms:kme (the column step)
+constexpr int kNeedLevel2 = 2;       // level 2 inside kms:kme (forcing_prep, forcing_interpolate_prep)
+constexpr int kNeedInitTile = 4;     // the tile is its..min(ite, ide-1) x jts..min(jte, jde-1) (noahmp_hip_init)
+int check_index_block(const noahmp_step_args* a, int need, const char* who);
 // sum the slots of h_counts into out[0..3]
 void sum_counts(long long* out);
 void status_counts(noahmp_status* st);     // ... into the int32 members of a status (saturated)

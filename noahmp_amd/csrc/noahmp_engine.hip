@@ -78,6 +78,47 @@ int ensure_bytes(void** p, size_t* have, size_t need) {
   *have = need;
   return 0;
 }
+
+// The index blocks the library accepts (the header text of noahmp_step_args states the rules).  Host arithmetic only: every entry point
+// that takes a step block calls this BEFORE ensure_init(), so a refused block touches neither the device nor the caller's arrays.
+int check_index_block(const noahmp_step_args* a, int need, const char* who) {
+  char b[320];
+  auto refuse = [&](const char* bound, const char* why) {
+    snprintf(b, sizeof b,
+             "%s: index block refused, %s: %s (ims:ime = %d:%d, jms:jme = %d:%d, kms:kme = %d:%d, its:ite = %d:%d, jts:jte = %d:%d, kts = %d)",
+             who, bound, why, a->ims, a->ime, a->jms, a->jme, a->kms, a->kme, a->its, a->ite, a->jts, a->jte, a->kts);
+    g.last_error = b;
+    return -103;
+  };
+  if (!a) { g.last_error = std::string(who) + ": the argument block is required"; return -103; }
+  // memory extents (an empty memory block is one, a negative extent is none)
+  if ((long)a->ime < (long)a->ims - 1) return refuse("ime", "ime < ims - 1");
+  if ((long)a->jme < (long)a->jms - 1) return refuse("jme", "jme < jms - 1");
+  if (a->kme < a->kms) return refuse("kme", "kme < kms");
+  // levels: level 1 is what every call reads or writes of the atmospheric arrays (drv:451-459)
+  if (a->kms > 1) return refuse("kms", "level 1 lies below kms");
+  if (a->kme < 1) return refuse("kme", "level 1 lies above kme");
+  if (need & kNeedLevel2) {             // the driver's level-2 copies (hdrv:336-344)
+    if (a->kme < 2) return refuse("kme", "level 2 lies above kme");
+  }
+  if (need & kNeedStepLevels) {         // SFCPRS = (P8W3D(kts+1) + P8W3D(kts)) * 0.5, drv:463
+    if (a->kts < a->kms) return refuse("kts", "kts lies below kms");
+    if ((long)a->kts + 1 > (long)a->kme) return refuse("kts", "kts + 1 lies above kme");
+  }
+  // tile: a non-empty one lies inside the memory block; NOAHMP_INIT loops to itf = min(ite, ide-1), jtf = min(jte, jde-1) (drv:991-992)
+  long ite = a->ite, jte = a->jte;
+  if (need & kNeedInitTile) {
+    if ((long)a->ide - 1 < ite) ite = (long)a->ide - 1;
+    if ((long)a->jde - 1 < jte) jte = (long)a->jde - 1;
+  }
+  if (ite < a->its || jte < a->jts) return 0;          // an empty tile: nothing is addressed
+  const bool init = (need & kNeedInitTile) != 0;
+  if (a->its < a->ims) return refuse("its", "its lies below ims");
+  if (ite > a->ime) return refuse(init ? "itf" : "ite", init ? "itf = min(ite, ide-1) lies above ime" : "ite lies above ime");
+  if (a->jts < a->jms) return refuse("jts", "jts lies below jms");
+  if (jte > a->jme) return refuse(init ? "jtf" : "jte", init ? "jtf = min(jte, jde-1) lies above jme" : "jte lies above jme");
+  return 0;
+}
 }  // namespace nmp_host
 
 using nmp_host::g;
@@ -253,6 +294,7 @@ int noahmp_hip_set_option(const char* key, int value) {
 #endif
   }
   else if (!strcmp(key, "exact_libm")) prev = NMP_EXACT_LIBM;   // read-only: how this library was built
+  else if (!strcmp(key, "last_host_path")) prev = g.last_host_path;   // read-only: which host-memory path the last noahmp_hip_step took
   return prev;
 }
 
@@ -445,6 +487,7 @@ static int pipeline_chunks(const noahmp_step_args* a) {
 static int step_host_pipelined(const noahmp_step_args* a, hipStream_t s, noahmp_status* st) {
   KArgs k;
   fill_kargs(k, a);
+  g.last_host_path = 2;
   const int nj_mem = a->jme - a->jms + 1;
   if (!g.s_up) { HIPCHK(hipStreamCreateWithFlags(&g.s_up, hipStreamNonBlocking)); HIPCHK(hipStreamCreateWithFlags(&g.s_dn, hipStreamNonBlocking)); }
   const int want = pipeline_chunks(a);
@@ -776,6 +819,7 @@ static int step_host_resident(const noahmp_step_args* a, hipStream_t s, noahmp_s
     const long sl = g.sorted_land, sg = g.sorted_glacier;     // the caller's own declaration (device-resident calls) is not touched
     if (run_sorted) { g.sorted_land = g.s_land; g.sorted_glacier = g.s_glacier; }
     launch_any(k, s, run_sorted);
+    g.last_host_path = run_sorted ? 4 : 3;
     if (run_sorted) { g.sorted_land = sl; g.sorted_glacier = sg; g.sorted_newer = true; g.calls_since_sort++; }
     g.last_step_sorted = run_sorted;
   }
@@ -850,7 +894,9 @@ int noahmp_hip_fetch(const noahmp_step_args* a) {
 
 int noahmp_hip_step(const noahmp_step_args* a, int mem, void* stream, noahmp_status* st) {
   if (st) memset(st, 0, sizeof(*st));
-  int rc = ensure_init();
+  int rc = nmp_host::check_index_block(a, nmp_host::kNeedStepLevels, "noahmp_hip_step");
+  if (rc) return rc;
+  rc = ensure_init();
   if (rc) return rc;
   rc = check_step_args(a, st);
   if (rc) return rc;
@@ -887,6 +933,7 @@ int noahmp_hip_step(const noahmp_step_args* a, int mem, void* stream, noahmp_sta
 
   if (mem == NOAHMP_MEM_HOST) {
     g.out_mirror_valid = false;
+    g.last_host_path = 1;
     // stage every array H2D into persistent device mirrors (caller's arrays stay the source of truth); pageable arrays travel through
     // the engine's own page-locked bounce buffers (nmp_stage.hpp), never through the runtime's pageable path
     std::vector<nmp_host::CopySeg> up;
@@ -950,7 +997,9 @@ int noahmp_hip_step(const noahmp_step_args* a, int mem, void* stream, noahmp_sta
 // accumulate on the device until noahmp_hip_sync(); the error word carries the step ordinal above the column index,
 // so the earliest step wins, then the first column in loop order -- the column the reference would have STOPped at.
 int noahmp_hip_step_async(const noahmp_step_args* a, void* stream) {
-  int rc = ensure_init();
+  int rc = nmp_host::check_index_block(a, nmp_host::kNeedStepLevels, "noahmp_hip_step_async");
+  if (rc) return rc;
+  rc = ensure_init();
   if (rc) return rc;
   rc = check_step_args(a, nullptr);
   if (rc) return rc;
@@ -1049,9 +1098,13 @@ int noahmp_hip_stream_sync(void* stream) {
 
 // dst column p <- src column perm[p] for every array of the step block ((re-)sorting a device-resident run)
 int noahmp_hip_permute_step_arrays(const noahmp_step_args* src, const noahmp_step_args* dst, const int32_t* perm, void* stream) {
+  int rc = nmp_host::check_index_block(src, 0, "noahmp_hip_permute_step_arrays (src)");
+  if (rc) return rc;
+  rc = nmp_host::check_index_block(dst, 0, "noahmp_hip_permute_step_arrays (dst)");
+  if (rc) return rc;
   g.cost_fresh = false;          // the cost record ("record_cost") is in the order the last step found the tile in
 
-  int rc = ensure_init();
+  rc = ensure_init();
   if (rc) return rc;
   if (src->ims != dst->ims || src->ime != dst->ime || src->jms != dst->jms || src->jme != dst->jme || src->nsoil != dst->nsoil ||
       src->kms != dst->kms || src->kme != dst->kme) {

@@ -387,8 +387,7 @@ static int fill_forcing_args(ForcingArgs& k, const noahmp_step_args* a, const fl
   k.first_step = (flags & NOAHMP_PREP_FIRST_STEP) ? 1 : 0;
   k.ni = a->ime - a->ims + 1;
   k.nka = a->kme - a->kms + 1;
-  k.k1 = 1 - a->kms;
-  if (k.nka < 2) { g.last_error = "forcing_prep needs two atmospheric levels (kms:kme)"; return -105; }
+  k.k1 = 1 - a->kms;          // levels 1 and 2 lie inside kms:kme: nmp_host::check_index_block(kNeedLevel2) at the entry points
   return 0;
 }
 static int fill_interp_args(InterpArgs& k, const noahmp_step_args* a, const noahmp_forcing_record* ra, const noahmp_forcing_record* rb,
@@ -448,7 +447,9 @@ int noahmp_hip_forcing_prep(const noahmp_step_args* a, const float* lon2d, const
                             int iminute, int isecond, float zlvl, int flags, float* julian_out, int mem,
                             void* stream, noahmp_status* st) {
   if (st) memset(st, 0, sizeof(*st));
-  int rc = nmp_host::ensure_init();
+  int rc = nmp_host::check_index_block(a, nmp_host::kNeedLevel2, "noahmp_hip_forcing_prep");
+  if (rc) return rc;
+  rc = nmp_host::ensure_init();
   if (rc) return rc;
   if (mem != NOAHMP_MEM_DEVICE) {
     g.last_error = "noahmp_hip_forcing_prep works on device-resident arrays only (a host caller keeps hdrv:336-354)";
@@ -465,7 +466,9 @@ int noahmp_hip_forcing_prep(const noahmp_step_args* a, const float* lon2d, const
 int noahmp_hip_forcing_interpolate(const noahmp_step_args* a, const noahmp_forcing_record* ra, const noahmp_forcing_record* rb,
                                    int idts, int idts2, float* rain_rate_out, int mem, void* stream, noahmp_status* st) {
   if (st) memset(st, 0, sizeof(*st));
-  int rc = nmp_host::ensure_init();
+  int rc = nmp_host::check_index_block(a, 0, "noahmp_hip_forcing_interpolate");
+  if (rc) return rc;
+  rc = nmp_host::ensure_init();
   if (rc) return rc;
   if (mem != NOAHMP_MEM_DEVICE) {
     g.last_error = "noahmp_hip_forcing_interpolate works on device-resident arrays only (a host caller keeps hrldas_input_read)";
@@ -485,7 +488,9 @@ int noahmp_hip_forcing_interpolate_prep(const noahmp_step_args* a, const noahmp_
                                         int idts, int idts2, float* rain_rate, const float* lon2d, int iday, int ihour, int iminute,
                                         int isecond, float zlvl, int flags, float* julian_out, int mem, void* stream, noahmp_status* st) {
   if (st) memset(st, 0, sizeof(*st));
-  int rc = nmp_host::ensure_init();
+  int rc = nmp_host::check_index_block(a, nmp_host::kNeedLevel2, "noahmp_hip_forcing_interpolate_prep");
+  if (rc) return rc;
+  rc = nmp_host::ensure_init();
   if (rc) return rc;
   if (mem != NOAHMP_MEM_DEVICE) {
     g.last_error = "noahmp_hip_forcing_interpolate_prep works on device-resident arrays only";

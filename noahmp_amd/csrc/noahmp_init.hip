@@ -44,7 +44,9 @@ extern "C" int noahmp_hip_init(const noahmp_step_args* a, int iswater, int fndsn
                                noahmp_status* st) {
   (void)iswater;
   if (st) memset(st, 0, sizeof(*st));
-  int rc = nmp_host::ensure_init();
+  int rc = nmp_host::check_index_block(a, nmp_host::kNeedInitTile, "noahmp_hip_init");
+  if (rc) return rc;
+  rc = nmp_host::ensure_init();
   if (rc) return rc;
   if (!g.have_tables) { g.last_error = "noahmp_hip_set_tables() has not been called"; return -102; }
   if (a->nsoil != NOAHMP_NSOIL) { if (st) st->code = NOAHMP_ERR_NSOIL_UNSUPPORTED; return NOAHMP_ERR_NSOIL_UNSUPPORTED; }

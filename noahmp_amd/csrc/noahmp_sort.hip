@@ -237,7 +237,9 @@ static int ensure_async_count() {
 
 int noahmp_hip_sort_columns(const noahmp_step_args* a, int flags, int tsk_bin_mk, int32_t* perm_out, uint32_t* keys_out,
                             int64_t* class_counts, void* stream) {
-  int rc = nmp_host::ensure_init();
+  int rc = nmp_host::check_index_block(a, 0, "noahmp_hip_sort_columns");
+  if (rc) return rc;
+  rc = nmp_host::ensure_init();
   if (rc) return rc;
   KeyArgs k;
   rc = fill_key_args(k, a, flags, tsk_bin_mk);
@@ -272,7 +274,9 @@ int noahmp_hip_sort_columns(const noahmp_step_args* a, int flags, int tsk_bin_mk
 }
 
 int noahmp_hip_sort_staleness(const noahmp_step_args* a, int flags, const uint32_t* sorted_keys, int64_t* changed, void* stream) {
-  int rc = nmp_host::ensure_init();
+  int rc = nmp_host::check_index_block(a, 0, "noahmp_hip_sort_staleness");
+  if (rc) return rc;
+  rc = nmp_host::ensure_init();
   if (rc) return rc;
   KeyArgs k;
   rc = fill_key_args(k, a, flags, 0);
@@ -296,7 +300,9 @@ int noahmp_hip_sort_staleness(const noahmp_step_args* a, int flags, const uint32
 // The same count without a wait: a check every K steps that drains the stream costs a run ~0.4 ms of idle GPU each time (the host has to
 // refill the queue); enqueued here, the count is read K steps later, when it has long arrived.
 int noahmp_hip_sort_staleness_async(const noahmp_step_args* a, int flags, const uint32_t* sorted_keys, void* stream) {
-  int rc = nmp_host::ensure_init();
+  int rc = nmp_host::check_index_block(a, 0, "noahmp_hip_sort_staleness_async");
+  if (rc) return rc;
+  rc = nmp_host::ensure_init();
   if (rc) return rc;
   KeyArgs k;
   rc = fill_key_args(k, a, flags, 0);
