@@ -1,0 +1,127 @@
+// Terrain-adjusted wind of the forcing (no reference counterpart; the contract is the text in include/noahmp_hip.h, the arithmetic is
+// nmp_dev_wind.hpp): the MicroMet wind model with the two maxima given by the caller.
+//
+// noahmp_hip_wind_terrain: ONE launch per call, once per terrain.  One thread per window cell in row-major order: the lanes of a wave are
+// neighbours along i, so each of the 13 heights a cell reads (the cell, its 4 neighbours at distance 1, its 8 at distance ncurv) is one
+// row segment per wave, shifted by a constant -- coalesced, and shared with the neighbouring rows' workgroups through the L2: from memory
+// the plane is read about once.  Three stores of 4 bytes per written cell.
+// noahmp_hip_forcing_wind: ONE launch per call, one column per thread: 5 loads and 2 stores of 4 bytes, 28 bytes per column, and about 40
+// float operations, three divisions (four with TURN), one square root and (with TURN) one sinf / cosf pair on an argument of about 0.25
+// at most: 4.8 TB/s with the turn, 5.1 without at 7 077 888 columns, 0.89 / 0.94 of what noahmp_hip_forcing_radiation_sky reaches in the
+// same run (profiles/wind_bench.md).
+// Neither kernel uses LDS, a barrier, atomics or scratch.  Arguments go by value, nothing is allocated, nothing waits on the host.
+#include <math.h>
+#include <string.h>
+#include <hip/hip_runtime.h>
+#include "noahmp_hip.h"
+#include "nmp_dev_wind.hpp"
+#include "nmp_engine_host.hpp"
+
+using namespace nmp;
+using nmp_host::g;
+
+namespace {
+
+constexpr int kBlock = 256;
+
+struct WindTerrainKArgs {
+  const float* height; const float* cosalpha; const float* sinalpha;
+  const int* dst_index;
+  float* sx; float* sy; float* curv;
+  long ncell, ndst;
+  WindTerrainParams p;
+};
+
+__global__ void __launch_bounds__(kBlock) noahmp_wind_terrain_kernel(const WindTerrainKArgs k) {
+  const long c = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= k.ncell) return;
+  const long d = k.dst_index ? (long)k.dst_index[c] : c;
+  if (d < 0 || d >= k.ndst) return;                              // a margin cell: read by others and not written
+  float ca = 1.f, sa = 0.f;
+  if (k.p.has_rot) { ca = k.cosalpha[c]; sa = k.sinalpha[c]; }
+  const int j = (int)(c / k.p.ni), i = (int)(c - (long)j * k.p.ni);
+  const WindSlope s = wind_terrain_cell(k.p, k.height, ca, sa, i, j);
+  k.sx[d] = s.sx;
+  k.sy[d] = s.sy;
+  k.curv[d] = s.curv;
+}
+
+struct WindKArgs {
+  float* u; float* v;
+  const float* sx; const float* sy; const float* curv;
+  long ncell;
+  WindParams p;
+};
+
+__global__ void __launch_bounds__(kBlock) noahmp_forcing_wind_kernel(const WindKArgs k) {
+  const long c = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= k.ncell) return;
+  float u = k.u[c], v = k.v[c];
+  if (!wind_column(k.p, k.sx[c], k.sy[c], k.curv[c], &u, &v)) return;      // the column keeps its bits: nothing is written
+  k.u[c] = u;
+  k.v[c] = v;
+}
+
+int refuse(const char* call, const char* what) {
+  char b[240];
+  snprintf(b, sizeof b, "%s: %s", call, what);
+  g.last_error = b;
+  return -105;
+}
+
+}  // namespace
+
+extern "C" {
+
+int noahmp_hip_wind_terrain(const noahmp_wind_terrain* wt, int64_t ndst, void* stream) {
+  const char* me = "noahmp_hip_wind_terrain";
+  if (!wt) return refuse(me, "the argument block is NULL");
+  if (!wt->height || !wt->sx || !wt->sy || !wt->curv) return refuse(me, "height, sx, sy and curv are required");
+  if ((wt->cosalpha != nullptr) != (wt->sinalpha != nullptr)) return refuse(me, "cosalpha and sinalpha go together: both or none");
+  if (wt->ni < 0 || wt->nj < 0 || (int64_t)wt->ni * (int64_t)wt->nj > 0x7FFFFFFFL) return refuse(me, "window: ni, nj >= 0 and ni*nj <= 2^31 - 1");
+  if (wt->ncurv < 1 || wt->ncurv > NOAHMP_WIND_MAX_NCURV) {
+    char b[120];
+    snprintf(b, sizeof b, "ncurv %d (1 .. %d cells)", wt->ncurv, NOAHMP_WIND_MAX_NCURV);
+    return refuse(me, b);
+  }
+  if (!(isfinite(wt->dx) && wt->dx > 0.f && isfinite(wt->dy) && wt->dy > 0.f)) return refuse(me, "dx and dy must be finite and > 0");
+  if (ndst < 0 || ndst > 0x7FFFFFFFL) return refuse(me, "ndst: 0 .. 2^31 - 1");
+  int rc = nmp_host::ensure_init();
+  if (rc) return rc;
+  const long ncell = (long)wt->ni * wt->nj;
+  if (ndst == 0 || ncell == 0) return 0;
+  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  WindTerrainKArgs k;
+  memset(&k, 0, sizeof(k));
+  k.height = wt->height; k.cosalpha = wt->cosalpha; k.sinalpha = wt->sinalpha; k.dst_index = wt->dst_index;
+  k.sx = wt->sx; k.sy = wt->sy; k.curv = wt->curv; k.ncell = ncell; k.ndst = ndst;
+  k.p = wind_terrain_params(wt->ni, wt->nj, wt->ncurv, wt->cosalpha ? 1 : 0, wt->dx, wt->dy);
+  hipLaunchKernelGGL(noahmp_wind_terrain_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int noahmp_hip_forcing_wind(const noahmp_wind* w, int64_t ncell, void* stream) {
+  const char* me = "noahmp_hip_forcing_wind";
+  if (!w) return refuse(me, "the argument block is NULL");
+  if (!w->u || !w->v || !w->sx || !w->sy || !w->curv) return refuse(me, "u, v, sx, sy and curv are required");
+  if (!(isfinite(w->slope_max) && w->slope_max > 0.f)) return refuse(me, "slope_max must be finite and > 0");
+  if (!(isfinite(w->curv_max) && w->curv_max > 0.f)) return refuse(me, "curv_max must be finite and > 0");
+  if (ncell < 0 || ncell > 0x7FFFFFFFL) return refuse(me, "ncell: 0 .. 2^31 - 1 columns");
+  int rc = nmp_host::ensure_init();
+  if (rc) return rc;
+  if (ncell == 0) return 0;
+  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  WindKArgs k;
+  memset(&k, 0, sizeof(k));
+  k.u = w->u; k.v = w->v; k.sx = w->sx; k.sy = w->sy; k.curv = w->curv; k.ncell = ncell;
+  k.p.ds = w->slope_max + w->slope_max;
+  k.p.dc = w->curv_max + w->curv_max;
+  k.p.gamma_s = w->gamma_s; k.p.gamma_c = w->gamma_c;
+  k.p.turn = (w->flags & NOAHMP_WIND_TURN) ? 1 : 0;
+  hipLaunchKernelGGL(noahmp_forcing_wind_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+}  // extern "C"

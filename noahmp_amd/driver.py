@@ -824,6 +824,50 @@ class Engine:
         if rc:
             raise RuntimeError("noahmp_hip_forcing_radiation_sky: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
+    # ---- terrain-adjusted wind: slope and curvature of the terrain, and the wind of a record (noahmp_wind.hip; helper: noahmp_amd/wind.py)
+    @staticmethod
+    def wind_terrain_block(height, sx, sy, curv, dx, dy, ncurv=3, cosalpha=None, sinalpha=None, dst_index=None):
+        """A noahmp_wind_terrain block over the (nj, ni) WINDOW plane height (float32, device): sx / sy / curv = the destination planes,
+        dst_index = int32 plane in window order (negative: a margin cell, read and not written) or None (identity); cosalpha / sinalpha:
+        WRF's rotation planes over the window, both or none.  The tensors are kept alive by the returned block."""
+        assert height.dim() == 2 and height.is_contiguous()
+        b = abi.WindTerrain()
+        keep = dict(height=height, cosalpha=cosalpha, sinalpha=sinalpha, dst_index=dst_index, sx=sx, sy=sy, curv=curv)
+        for name, t in keep.items():
+            setattr(b, name, t.data_ptr() if t is not None else None)
+        b.nj, b.ni = (int(v) for v in height.shape)
+        b.ncurv = int(ncurv)
+        b.dx, b.dy = float(dx), float(dy)
+        b._keep = keep
+        return b
+
+    def wind_terrain(self, block, ndst, stream=None):
+        """The slope vector (length = the slope angle, pointing uphill) and the curvature of a block of Engine.wind_terrain_block.  One
+        kernel launch, enqueued only, once per terrain (noahmp_hip_wind_terrain)."""
+        rc = self.lib.noahmp_hip_wind_terrain(C.byref(block), int(ndst), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_wind_terrain: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
+    @staticmethod
+    def wind_block(u, v, sx, sy, curv, slope_max, curv_max, gamma_s=0.58, gamma_c=0.42, turn=True):
+        """A noahmp_wind block: u / v are adjusted in place; sx / sy / curv are the planes of wind_terrain in the column order of u and v;
+        slope_max / curv_max the maxima of the whole run, the same numbers on every rank.  The tensors are kept alive by the block."""
+        b = abi.Wind()
+        keep = dict(u=u, v=v, sx=sx, sy=sy, curv=curv)
+        for name, t in keep.items():
+            setattr(b, name, t.data_ptr() if t is not None else None)
+        b.slope_max, b.curv_max, b.gamma_s, b.gamma_c = float(slope_max), float(curv_max), float(gamma_s), float(gamma_c)
+        b.flags = abi.WIND_FLAG["turn"] if turn else 0
+        b._keep = keep
+        return b
+
+    def forcing_wind(self, block, ncell, stream=None):
+        """The wind of ncell columns weighted by slope and curvature and (with the TURN flag) turned around the obstacle, in place, from a
+        block of Engine.wind_block: one kernel launch, enqueued only (noahmp_hip_forcing_wind)."""
+        rc = self.lib.noahmp_hip_forcing_wind(C.byref(block), int(ncell), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_forcing_wind: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""
