@@ -14,7 +14,7 @@ SOURCES = ["noahmp_engine.hip", "noahmp_groundwater.hip", "noahmp_init.hip", "no
            "noahmp_engine_d3_r1.hip", "noahmp_engine_d3_r5.hip", "noahmp_engine_d4_r1.hip", "noahmp_engine_d4_r3.hip",
            "noahmp_jit.hip", "noahmp_sort.hip", "noahmp_halo.hip", "noahmp_stage.hip", "noahmp_history.hip", "noahmp_regions.hip",
            "noahmp_regrid.hip", "noahmp_shortwave.hip", "noahmp_regrid_conserve.hip", "noahmp_shadow.hip",
-           "noahmp_skyview.hip", "noahmp_wind.hip"]
+           "noahmp_skyview.hip", "noahmp_wind.hip", "noahmp_routing.hip"]
 
 
 def _headers():
@@ -98,6 +98,30 @@ def build(force=False, verbose=False, extra_flags=(), lib=None, jobs=None):
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
+    return lib
+
+
+def build_unit_variant(src, extra_flags, lib, verbose=False):
+    """A library that differs from the default one in ONE translation unit: `src` compiled again with extra_flags and linked with the
+    default build's other objects (e.g. noahmp_routing.hip with -DNMP_ROUTE_LOAD_ALL=0: seconds instead of a second build of the engine).
+    Rebuilt when it is missing or older than `src` or a header.  Staleness looks at `src` and the headers only: a change of ANOTHER
+    translation unit that touches no header leaves the variant linked from that unit's old object until `src` or a header changes (or the
+    variant is deleted) -- harmless where, as for the routing kernels, the variant is used for the calls of `src` alone."""
+    if os.path.exists(lib) and not _stale(lib, [src] + _headers()):
+        return lib
+    build()
+    others = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in _sources() if s != src]
+    if not all(os.path.exists(o) for o in others):                    # a tree that carries the library without its objects
+        build(force=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objdir = lib + ".obj"
+    os.makedirs(objdir, exist_ok=True)
+    obj = os.path.join(objdir, src.replace(".hip", ".o"))
+    for cmd in ([hipcc] + FLAGS + list(extra_flags) + ["-c", os.path.join(CSRC, src), "-o", obj],
+                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + others + [obj, "-o", lib, "-lhiprtc", "-ldl", "-lpthread"]):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
     return lib
 
 

@@ -868,6 +868,79 @@ class Engine:
         if rc:
             raise RuntimeError("noahmp_hip_forcing_wind: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
+    # ---- runoff routing on a D8 network: directions, upstream bytes, upstream counts, linear reservoirs (noahmp_routing.hip; helper:
+    # noahmp_amd/routing.py)
+    @staticmethod
+    def flow_terrain_block(height, dir, dx, dy):
+        """A noahmp_flow_terrain block over the (nj, ni) WINDOW plane height (float32, device): dir = the uint8 destination plane of the
+        same shape.  The tensors are kept alive by the returned block."""
+        import torch
+        assert height.dim() == 2 and height.is_contiguous() and height.dtype == torch.float32
+        assert dir.dtype == torch.uint8 and dir.is_contiguous() and dir.numel() == height.numel()
+        b = abi.FlowTerrain()
+        b.height, b.dir = height.data_ptr(), dir.data_ptr()
+        b.nj, b.ni = (int(v) for v in height.shape)
+        b.dx, b.dy = float(dx), float(dy)
+        b._keep = (height, dir)
+        return b
+
+    def flow_terrain(self, block, stream=None):
+        """The direction of steepest strict descent (0 or k = 1..8) of every cell of a block of Engine.flow_terrain_block.  One kernel
+        launch, enqueued only, once per terrain (noahmp_hip_flow_terrain)."""
+        rc = self.lib.noahmp_hip_flow_terrain(C.byref(block), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_flow_terrain: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
+    def flow_inmask(self, dir, inmask, stream=None):
+        """The byte of upstream neighbours of every cell of the (nj, ni) uint8 device plane dir, into the uint8 plane inmask.  One kernel
+        launch, enqueued only (noahmp_hip_flow_inmask)."""
+        import torch
+        assert dir.dim() == 2 and dir.dtype == torch.uint8 and inmask.dtype == torch.uint8 and dir.is_contiguous() and inmask.is_contiguous()
+        assert inmask.numel() == dir.numel()
+        nj, ni = (int(v) for v in dir.shape)
+        rc = self.lib.noahmp_hip_flow_inmask(dir.data_ptr(), inmask.data_ptr(), ni, nj, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_flow_inmask: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
+    def flow_accumulate(self, inmask, acc_old, acc_new, changed, stream=None):
+        """One Jacobi pass of the upstream cell count over the (nj, ni) uint8 device plane inmask: acc_old -> acc_new (int32 tensors holding
+        uint32 words), changed = a device word that receives 1 when a cell changed.  One kernel launch, enqueued only
+        (noahmp_hip_flow_accumulate)."""
+        import torch
+        assert inmask.dim() == 2 and inmask.dtype == torch.uint8 and inmask.is_contiguous()
+        assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() == inmask.numel() for t in (acc_old, acc_new))
+        assert changed.dtype == torch.int32 and changed.numel() >= 1
+        nj, ni = (int(v) for v in inmask.shape)
+        rc = self.lib.noahmp_hip_flow_accumulate(inmask.data_ptr(), acc_old.data_ptr(), acc_new.data_ptr(), changed.data_ptr(), ni, nj, stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_flow_accumulate: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
+    @staticmethod
+    def route_block(inmask, col_index, area, release, storage, out_old, out_new, runoff_a, runoff_b, scale):
+        """A noahmp_route block over the (nj, ni) WINDOW: inmask uint8, col_index int32, the others float32 device planes of the window;
+        runoff_a / runoff_b (or None) in the column order of the store.  The tensors are kept alive by the returned block."""
+        import torch
+        assert inmask.dim() == 2 and inmask.dtype == torch.uint8 and col_index.dtype == torch.int32
+        keep = dict(inmask=inmask, col_index=col_index, area=area, release=release, storage=storage, out_old=out_old, out_new=out_new,
+                    runoff_a=runoff_a, runoff_b=runoff_b)
+        b = abi.Route()
+        for name, t in keep.items():
+            if t is not None:
+                assert t.is_contiguous() and (name.startswith("runoff") or t.numel() == inmask.numel()), name
+                assert name in ("inmask", "col_index") or t.dtype == torch.float32, name
+            setattr(b, name, t.data_ptr() if t is not None else None)
+        b.nj, b.ni = (int(v) for v in inmask.shape)
+        b.scale = float(scale)
+        b._keep = keep
+        return b
+
+    def route_runoff(self, block, ncol, stream=None):
+        """One routing step of a block of Engine.route_block: every owned cell gathers what its upstream neighbours released in the call
+        before, adds its column's runoff and releases its fraction.  One kernel launch, enqueued only (noahmp_hip_route_runoff)."""
+        rc = self.lib.noahmp_hip_route_runoff(C.byref(block), int(ncol), stream)
+        if rc:
+            raise RuntimeError("noahmp_hip_route_runoff: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

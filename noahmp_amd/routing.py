@@ -1,0 +1,267 @@
+"""Discharge of a device-resident run: cell-to-cell linear reservoirs on a D8 network (noahmp_hip_flow_terrain / _flow_inmask /
+_flow_accumulate / noahmp_hip_route_runoff).
+
+    net = FlowNetwork(engine, ni, nj)                              # the tile of the store
+    net.set_terrain(height, dx, dy, origin=(i0, j0))               # once: height is a WINDOW = tile + 2 cells where there is a neighbour
+    #   or: net.set_directions(FlowNetwork.from_esri(codes), origin=(i0, j0), dx=dx, dy=dy)      codes: a window = tile + 1-cell ring
+    net.set_area(area); net.set_velocity(0.5, dt)                  # m2 per cell; release = 1 - exp(-dt*v/length)
+    net.follow(store)                                              # after Engine.sort_store: only col_index is rewritten
+    engine.noahmplsm(store, ...); net.step(store, dt)              # per step: one launch (nsub launches), enqueued only
+    q = net.discharge()                                            # m3/s leaving every cell of the block in the last step
+
+Every cell gathers what its upstream neighbours released in the call before, adds (RUNSFXY + RUNSBXY) * dt * 1e-3 * area of its column
+and releases the fraction `release` of its storage; water leaves the network at the cells without a direction (outlets, pits, the coast).
+The window planes (the BLOCK: the tile plus a 1-cell ring where the window given has room for one) never move; a sorted store is followed
+through col_index alone.  Not represented: kinematic or diffusive wave, channel geometry, backwater, losses and lakes, a celerity above
+one cell per call (nsub sub-steps).  No pit filling, no flat resolution: a raw DEM is conditioned by the caller.  The contract -- every
+rounding -- is the text in include/noahmp_hip.h.
+"""
+import math
+
+import numpy as np
+
+ESRI_CODES = {1: 1, 128: 2, 64: 3, 32: 4, 16: 5, 8: 6, 4: 7, 2: 8}      # ESRI / WRF-Hydro FLOWDIRECTION (E = 1, clockwise) -> k, with j towards north
+NOT_OWNED = -2                                                           # col_index of a ring cell
+
+
+class FlowNetwork:
+    def __init__(self, engine, ni, nj):
+        import torch
+        self.engine, self.torch = engine, torch
+        self.ni, self.nj = int(ni), int(nj)
+        self.ncell = self.ni * self.nj
+        self.dir = self.inmask = None                                    # uint8, the block
+        self.i0 = self.j0 = 0                                            # the tile's cell (0, 0) inside the block
+        self.dx = self.dy = None
+        self.area = self.release = self.storage = None
+        self.out = None                                                  # the two out planes; out[cur] holds the last call's
+        self.cur = 0
+        self.col_index = None
+        self.has_input = None                                            # bool, tile order: None = every column
+        self._input_known = False                                        # False: step() derives has_input from its store
+        self.perm = None
+        self.last_dt = None
+        self.passes = 0                                                  # passes the last upstream_cells() made
+        self._area_default = True                                        # area is dx*dy of the last set_directions, not the caller's
+
+    # ---- the network
+    @staticmethod
+    def from_esri(codes):
+        """The 1 / 2 / 4 / ... / 128 codes of an ESRI / WRF-Hydro FLOWDIRECTION grid (rows from south to north, as the model's j) as
+        directions 0..8 (uint8, numpy or torch in, the same out).  Every other code (0, 255, nodata) becomes 0."""
+        lut = np.zeros(256, np.uint8)
+        for code, k in ESRI_CODES.items():
+            lut[code] = k
+        if isinstance(codes, np.ndarray):
+            c = codes.astype(np.int64)
+            return np.where((c >= 0) & (c < 256), lut[np.clip(c, 0, 255)], 0).astype(np.uint8)
+        import torch
+        c = codes.to(torch.int64)
+        t = torch.from_numpy(lut).to(codes.device)
+        return torch.where((c >= 0) & (c < 256), t[c.clamp(0, 255)], torch.zeros((), dtype=torch.uint8, device=codes.device))
+
+    def _block_of(self, shape, origin):
+        i0, j0 = (int(v) for v in origin)
+        nj_w, ni_w = shape
+        assert 0 <= i0 and i0 + self.ni <= ni_w and 0 <= j0 and j0 + self.nj <= nj_w, "the window must contain the tile at origin"
+        w, s = min(1, i0), min(1, j0)
+        e, n = min(1, ni_w - i0 - self.ni), min(1, nj_w - j0 - self.nj)
+        return (slice(j0 - s, j0 + self.nj + n), slice(i0 - w, i0 + self.ni + e)), (w, s)
+
+    def set_terrain(self, height, dx, dy, origin=(0, 0)):
+        """height: the terrain height [m] of an (nj_w, ni_w) float32 device WINDOW that contains the tile with its cell (0, 0) at window
+        cell origin = (i0, j0): the tile plus 2 cells on every side that is not an edge of the whole domain gives, on the block, the
+        directions of the undecomposed run.  Two launches, once."""
+        torch = self.torch
+        assert height.dim() == 2
+        h = height.to(torch.float32).contiguous()
+        d = torch.empty(h.shape, dtype=torch.uint8, device=h.device)
+        torch.cuda.current_stream().synchronize()
+        self.engine.flow_terrain(self.engine.flow_terrain_block(h, d, dx, dy))
+        self.engine.stream_sync()
+        self.set_directions(d, origin=origin, dx=dx, dy=dy)
+
+    def set_directions(self, dir_window, origin=(0, 0), dx=None, dy=None):
+        """dir_window: directions 0..8 (uint8 device plane, e.g. from_esri of a FLOWDIRECTION grid) of a window that contains the tile
+        at origin; the block is the tile plus the 1-cell ring the window has room for.  Raises on a value outside 0..8.  dx, dy [m]: for
+        set_velocity and the default area dx*dy; without them the caller gives set_area and set_release.  One launch."""
+        torch = self.torch
+        assert dir_window.dim() == 2 and dir_window.dtype == torch.uint8
+        if int(dir_window.max().item()) > 8:
+            raise ValueError("directions are 0 (none) or 1..8 (E, NE, N, NW, W, SW, S, SE); FlowNetwork.from_esri converts ESRI codes")
+        block, (self.i0, self.j0) = self._block_of(tuple(dir_window.shape), origin)
+        self.dir = dir_window[block].contiguous()
+        self.inmask = torch.empty_like(self.dir)
+        self.dx, self.dy = (float(dx), float(dy)) if dx is not None and dy is not None else (None, None)
+        torch.cuda.current_stream().synchronize()
+        self.engine.flow_inmask(self.dir, self.inmask)
+        self.engine.stream_sync()
+        dev = self.dir.device
+        zeros = lambda: torch.zeros(self.dir.shape, dtype=torch.float32, device=dev)      # noqa: E731
+        self.storage, self.out, self.cur = zeros(), [zeros(), zeros()], 0
+        if self._area_default or self.area is None or self.area.shape != self.dir.shape:      # the caller's area is kept, a default is remade
+            self.area = torch.full(self.dir.shape, self.dx * self.dy, dtype=torch.float32, device=dev) if self.dx is not None else None
+            self._area_default = True
+        if self.release is None or self.release.shape != self.dir.shape:
+            self.release = torch.ones(self.dir.shape, dtype=torch.float32, device=dev)
+        self._index()
+
+    @property
+    def block_shape(self):
+        return tuple(self.dir.shape)
+
+    def tile_view(self, plane):
+        """The tile's cells of a block plane."""
+        return plane[self.j0:self.j0 + self.nj, self.i0:self.i0 + self.ni]
+
+    def _index(self):
+        torch = self.torch
+        dev = self.dir.device
+        pos = torch.arange(self.ncell, dtype=torch.int32, device=dev)
+        if self.perm is not None:                                        # sorted position p holds tile column perm[p]
+            inv = torch.empty_like(pos)
+            inv[self.perm.long()] = pos
+            pos = inv
+        if self.has_input is not None:
+            pos = torch.where(self.has_input.reshape(-1), pos, torch.full_like(pos, -1))
+        idx = torch.full(self.dir.shape, NOT_OWNED, dtype=torch.int32, device=dev)
+        self.tile_view(idx).copy_(pos.reshape(self.nj, self.ni))
+        self.col_index = idx.contiguous()
+        torch.cuda.current_stream().synchronize()
+
+    def set_input_columns(self, has_input):
+        """has_input: bool plane of the tile in TILE order, False where a column has no local input (water and skipped columns, whose
+        RUNSFXY / RUNSBXY the step never writes), or None = every column."""
+        self.has_input = None if has_input is None else has_input.to(self.torch.bool).reshape(self.nj, self.ni)
+        self._input_known = True
+        if self.dir is not None:
+            self._index()
+
+    def follow(self, store):
+        """After Engine.sort_store(store): only col_index is rewritten, from the inverse permutation.  The window planes never move."""
+        perm = getattr(store, "sort_perm", None)
+        assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
+        assert store.ni == self.ni and store.nj == self.nj
+        self.perm = perm
+        if self.dir is not None:
+            self._index()
+
+    def upstream_cells(self, max_pass=None):
+        """The number of cells that drain through every cell of the block, itself included (uint32 words in an int32 device plane):
+        noahmp_hip_flow_accumulate until nothing changes, the flag read every 64 passes.  SINGLE-TILE: the block's edge counts as the
+        domain's; a decomposed caller exchanges acc after every pass and agrees on `changed` itself.  max_pass defaults to 4*(ni + nj)."""
+        torch = self.torch
+        nj, ni = self.block_shape
+        max_pass = 4 * (ni + nj) if max_pass is None else int(max_pass)
+        a = torch.ones((nj, ni), dtype=torch.int32, device=self.dir.device)
+        b = torch.empty_like(a)
+        changed = torch.zeros(1, dtype=torch.int32, device=self.dir.device)
+        torch.cuda.current_stream().synchronize()
+        done = 0
+        while done < max_pass:
+            n = min(64, max_pass - done)
+            for _ in range(n - 1):
+                self.engine.flow_accumulate(self.inmask, a, b, changed)
+                a, b = b, a
+            self.engine.stream_sync()
+            changed.zero_()                                              # the flag of the LAST pass of the batch decides
+            torch.cuda.current_stream().synchronize()
+            self.engine.flow_accumulate(self.inmask, a, b, changed)
+            a, b = b, a
+            self.engine.stream_sync()
+            done += n
+            self.passes = done
+            if int(changed.item()) == 0:
+                return a
+        raise RuntimeError("upstream_cells: still changing after %d passes: the flow paths are longer than that, or caller-given "
+                           "directions hold a cycle" % max_pass)
+
+    # ---- the reservoirs
+    def _plane(self, plane, name):
+        torch = self.torch
+        if not torch.is_tensor(plane):
+            plane = torch.full(self.block_shape, float(plane), dtype=torch.float32, device=self.dir.device)
+        plane = plane.to(torch.float32)
+        if tuple(plane.shape) == (self.nj, self.ni) and self.block_shape != (self.nj, self.ni):
+            full = torch.zeros(self.block_shape, dtype=torch.float32, device=self.dir.device)
+            self.tile_view(full).copy_(plane)
+            plane = full
+        assert tuple(plane.shape) == self.block_shape, "%s: a plane of the block %s or of the tile" % (name, self.block_shape)
+        return plane.contiguous()
+
+    def set_area(self, plane):
+        """Cell area [m2]: a number, or a float32 device plane of the block or of the tile."""
+        self.area = self._plane(plane, "area")
+        self._area_default = False
+
+    def set_release(self, plane):
+        """The fraction of its storage every cell releases per call, in [0, 1] (not checked; 0 holds the water)."""
+        self.release = self._plane(plane, "release")
+
+    def set_velocity(self, velocity, dt):
+        """release = 1 - exp(-dt*velocity/length), made in float64 on the host and rounded once; length = dx, dy or the diagonal by the
+        cell's direction (dx where it has none).  velocity [m/s]: a number or a plane of the block or the tile."""
+        assert self.dx is not None, "set_velocity needs the dx, dy of set_terrain / set_directions"
+        v = self._plane(velocity, "velocity").cpu().numpy().astype(np.float64)
+        d = self.dir.cpu().numpy()
+        diag = math.sqrt(self.dx * self.dx + self.dy * self.dy)
+        length = np.where(d == 0, self.dx, np.where(d % 2 == 0, diag, np.where((d == 3) | (d == 7), self.dy, self.dx)))
+        r = (1.0 - np.exp(-float(dt) * v / length)).astype(np.float32)
+        self.release = self.torch.from_numpy(r).to(self.dir.device).contiguous()
+
+    def step(self, store, dt, fields=("runsfxy", "runsbxy"), nsub=1, comm=None, geom=None, stream=None):
+        """One model step of routing after Engine.noahmplsm: nsub launches with scale = dt*1e-3/nsub, ping-ponging the two out planes;
+        with a comm, comm.exchange_halo([out], geom) refreshes the ring after every launch.  fields: one or two planes of the store in
+        mm/s.  Without a comm the launches are enqueued only, on `stream` (None: the engine's own).
+        THE STREAM RULE with a comm: the exchange is enqueued on torch's CURRENT stream (the RCCL and IPC transports return before their
+        copies are done), which is in general not the stream the launch runs on.  So after every launch step() waits for `stream`, runs
+        the exchange, and waits for torch's current stream: the next launch -- the next sub-step, or the next step's -- reads a ring that
+        has arrived, whatever the two streams are."""
+        if self.dir is None:
+            raise ValueError("call set_terrain() or set_directions() first")
+        if self.area is None:
+            raise ValueError("directions were given without dx, dy: call set_area() first")
+        assert store.ni == self.ni and store.nj == self.nj and 1 <= len(fields) <= 2 and nsub >= 1
+        if not self._input_known:
+            self._auto_input(store)                                      # once: the columns the step advances
+        ra = store.a[fields[0]]
+        rb = store.a[fields[1]] if len(fields) > 1 else None
+        scale = float(np.float32(dt) * np.float32(1e-3)) / nsub
+        for _ in range(int(nsub)):
+            new = 1 - self.cur
+            b = self.engine.route_block(self.inmask, self.col_index, self.area, self.release, self.storage, self.out[self.cur], self.out[new],
+                                        ra, rb, scale)
+            self.engine.route_runoff(b, self.ncell, stream=stream)
+            self.cur = new
+            if comm is not None:
+                self.engine.stream_sync(stream)                          # out[new] is written before it travels
+                comm.exchange_halo([self.out[new]], geom)
+                self.torch.cuda.current_stream().synchronize()           # ... and its ring has arrived before anybody reads it
+        self.last_dt = float(dt) / nsub
+
+    def _auto_input(self, store):
+        """Columns with XLAND >= 1.5 (water) or XICE >= XICE_THRES (sea ice) are skipped by the step (drv:426-441): no local input."""
+        torch = self.torch
+        xland, xice = store.a["xland"].reshape(-1), store.a["xice"].reshape(-1)
+        has = ((xland - 1.5) < 0) & ~(xice >= float(store.cfg.xice_thres))
+        if self.perm is not None:                                        # the store is sorted: back to tile order
+            tile = torch.empty_like(has)
+            tile[self.perm.long()] = has
+            has = tile
+        self.set_input_columns(has.reshape(self.nj, self.ni))
+
+    def discharge(self):
+        """out / dt of the last call [m3/s], a plane of the block: at the cells without a direction it is the water leaving the network."""
+        assert self.last_dt, "no step yet"
+        return self.out[self.cur] / self.last_dt
+
+    def state_dict(self):
+        """The restart state: storage and the current out plane (copies)."""
+        return dict(storage=self.storage.clone(), out=self.out[self.cur].clone())
+
+    def load_state_dict(self, state):
+        self.torch.cuda.current_stream().synchronize()
+        self.engine.stream_sync()
+        self.storage.copy_(state["storage"])
+        self.out[self.cur].copy_(state["out"])
+        self.torch.cuda.current_stream().synchronize()
