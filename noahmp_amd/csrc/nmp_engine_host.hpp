@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <math.h>
 #include <stdio.h>
 #include <string>
 #include <unordered_map>
@@ -163,5 +164,16 @@ void sum_counts(long long* out);
 void status_counts(noahmp_status* st);     // ... into the int32 members of a status (saturated)
 // grow-only device buffer
 int ensure_bytes(void** p, size_t* have, size_t need);
+
+// What the entry points of the forcing and terrain units share on the host.  Each unit keeps its own wording: the checks return bool and
+// the caller supplies the text.
+// g.last_error = the formatted text; returns rc.  Texts are cut at 255 characters; the longest present one is noahmp_hip_regrid_conserve_plan's
+// "the workspace has %lld words, noahmp_hip_regrid_conserve_plan_size asks for %lld": 108 characters and two counts of at most 20.
+int refuse(int rc, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+inline bool bad_count(int64_t n) { return n < 0 || n > 0x7FFFFFFFL; }                                   // outside 0 .. 2^31 - 1
+inline bool bad_window(int ni, int nj) { return ni < 0 || nj < 0 || bad_count((int64_t)ni * (int64_t)nj); }
+inline bool bad_spacing(float dx, float dy) { return !(isfinite(dx) && dx > 0.f && isfinite(dy) && dy > 0.f); }
+inline hipStream_t stream_of(void* stream) { return stream ? (hipStream_t)stream : g.own_stream; }
+inline dim3 grid_1d(long n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
 
 }  // namespace nmp_host

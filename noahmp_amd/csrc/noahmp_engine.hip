@@ -6,6 +6,7 @@
 // read / written in the caller's own Fortran layout, whose i-contiguous rows are already the
 // coalesced structure-of-arrays the GPU wants.  No CPU fallback exists in this library.
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -77,6 +78,16 @@ int ensure_bytes(void** p, size_t* have, size_t need) {
   HIPCHK(hipMalloc(p, need));
   *have = need;
   return 0;
+}
+
+int refuse(int rc, const char* fmt, ...) {
+  char b[256];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(b, sizeof b, fmt, ap);
+  va_end(ap);
+  g.last_error = b;
+  return rc;
 }
 
 // The index blocks the library accepts (the header text of noahmp_step_args states the rules).  Host arithmetic only: every entry point

@@ -14,7 +14,7 @@
 #include "nmp_engine_host.hpp"
 
 using namespace nmp;
-using nmp_host::g;
+using nmp_host::g, nmp_host::refuse, nmp_host::bad_count, nmp_host::bad_window, nmp_host::stream_of, nmp_host::grid_1d;
 
 namespace {
 
@@ -161,13 +161,12 @@ __global__ void __launch_bounds__(kBlock) noahmp_history_finish_kernel(const Fin
 }
 
 int check_entries(const char* who, int n, const noahmp_history_entry* e) {
-  char b[200];
-  if (n < 0 || n > kMaxEntries) { snprintf(b, sizeof b, "%s: 0..%d entries per call (n = %d)", who, kMaxEntries, n); g.last_error = b; return -107; }
-  if (n > 0 && !e) { snprintf(b, sizeof b, "%s: entries are NULL", who); g.last_error = b; return -105; }
+  if (n < 0 || n > kMaxEntries) return refuse(-107, "%s: 0..%d entries per call (n = %d)", who, kMaxEntries, n);
+  if (n > 0 && !e) return refuse(-105, "%s: entries are NULL", who);
   for (int f = 0; f < n; f++) {
-    if (e[f].op < NOAHMP_HIST_SUM || e[f].op > NOAHMP_HIST_LAST) { snprintf(b, sizeof b, "%s: entry %d has op %d (NOAHMP_HIST_SUM .. NOAHMP_HIST_LAST)", who, f, e[f].op); g.last_error = b; return -105; }
-    if (!e[f].acc) { snprintf(b, sizeof b, "%s: entry %d has a NULL plane", who, f); g.last_error = b; return -105; }
-    if (e[f].nlev < 1 || e[f].nlev > kMaxLevels) { snprintf(b, sizeof b, "%s: entry %d has %d levels (1..%d)", who, f, e[f].nlev, kMaxLevels); g.last_error = b; return -105; }
+    if (e[f].op < NOAHMP_HIST_SUM || e[f].op > NOAHMP_HIST_LAST) return refuse(-105, "%s: entry %d has op %d (NOAHMP_HIST_SUM .. NOAHMP_HIST_LAST)", who, f, e[f].op);
+    if (!e[f].acc) return refuse(-105, "%s: entry %d has a NULL plane", who, f);
+    if (e[f].nlev < 1 || e[f].nlev > kMaxLevels) return refuse(-105, "%s: entry %d has %d levels (1..%d)", who, f, e[f].nlev, kMaxLevels);
   }
   return 0;
 }
@@ -181,32 +180,29 @@ extern "C" {
 int noahmp_hip_history_step(int n, const noahmp_history_entry* e, const noahmp_history_probes* p, const noahmp_step_args* a,
                             int32_t* count, void* stream) {
   static const char* who = "noahmp_hip_history_step";
-  char b[200];
   int rc = check_entries(who, n, e);
   if (rc) return rc;
   for (int f = 0; f < n; f++)
-    if (!e[f].src) { snprintf(b, sizeof b, "%s: entry %d has a NULL plane", who, f); g.last_error = b; return -105; }
-  if (!a || !a->xland || !a->xice) { g.last_error = "noahmp_hip_history_step: the step block and its XLAND / XICE planes are required"; return -105; }
-  if (a->ims != a->its || a->ime != a->ite || a->jms != a->jts || a->jme != a->jte) {
-    g.last_error = "noahmp_hip_history_step: the memory block must be the tile";
-    return -105;
-  }
+    if (!e[f].src) return refuse(-105, "%s: entry %d has a NULL plane", who, f);
+  if (!a || !a->xland || !a->xice) return refuse(-105, "noahmp_hip_history_step: the step block and its XLAND / XICE planes are required");
+  if (a->ims != a->its || a->ime != a->ite || a->jms != a->jts || a->jme != a->jte)
+    return refuse(-105, "noahmp_hip_history_step: the memory block must be the tile");
   const int ni = a->ime - a->ims + 1, nj = a->jme - a->jms + 1;
   const long ncol = (long)ni * nj;
-  if (ni < 0 || nj < 0 || ncol > 0x7FFFFFFFL) { g.last_error = "noahmp_hip_history_step: 0 .. 2^31 - 1 columns"; return -105; }
+  if (bad_window(ni, nj)) return refuse(-105, "noahmp_hip_history_step: 0 .. 2^31 - 1 columns");
   if (p) {
-    if (p->npoint < 0 || p->npoint > kMaxPoints) { snprintf(b, sizeof b, "%s: 0..%d probe points (npoint = %d)", who, kMaxPoints, p->npoint); g.last_error = b; return -107; }
-    if (p->nfield < 0 || p->nfield > kMaxProbeFields) { snprintf(b, sizeof b, "%s: 0..%d probe fields (nfield = %d)", who, kMaxProbeFields, p->nfield); g.last_error = b; return -107; }
+    if (p->npoint < 0 || p->npoint > kMaxPoints) return refuse(-107, "%s: 0..%d probe points (npoint = %d)", who, kMaxPoints, p->npoint);
+    if (p->nfield < 0 || p->nfield > kMaxProbeFields) return refuse(-107, "%s: 0..%d probe fields (nfield = %d)", who, kMaxProbeFields, p->nfield);
     if (p->npoint > 0 && p->nfield > 0) {
-      if (!p->column || !p->field || !p->ring) { g.last_error = "noahmp_hip_history_step: probes need column, field and ring"; return -105; }
-      if (p->nslot < 1 || p->slot < 0) { g.last_error = "noahmp_hip_history_step: probes need nslot >= 1 and slot >= 0"; return -105; }
+      if (!p->column || !p->field || !p->ring) return refuse(-105, "noahmp_hip_history_step: probes need column, field and ring");
+      if (p->nslot < 1 || p->slot < 0) return refuse(-105, "noahmp_hip_history_step: probes need nslot >= 1 and slot >= 0");
       for (int f = 0; f < p->nfield; f++)
-        if (!p->field[f]) { snprintf(b, sizeof b, "%s: probe field %d is a NULL plane", who, f); g.last_error = b; return -105; }
+        if (!p->field[f]) return refuse(-105, "%s: probe field %d is a NULL plane", who, f);
     }
   }
   rc = nmp_host::ensure_init();
   if (rc) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   StepKArgs k;
   memset(&k, 0, sizeof(k));
   bool vec = aligned16(a->xland) && aligned16(a->xice) && aligned16(count);
@@ -219,13 +215,13 @@ int noahmp_hip_history_step(int n, const noahmp_history_entry* e, const noahmp_h
   k.xland = a->xland; k.xice = a->xice; k.count = count; k.xice_thres = a->xice_thres;
   k.n = n; k.ni = ni; k.ncol = ncol;
   const long nthread = (n > 0 || count) ? (vec ? (ncol + 3) / 4 : ncol) : 0;
-  k.col_blocks = (unsigned)((nthread + kBlock - 1) / kBlock);
+  k.col_blocks = grid_1d(nthread, kBlock).x;
   unsigned probe_blocks = 0;
   if (p && p->npoint > 0 && p->nfield > 0) {
     for (int f = 0; f < p->nfield; f++) k.field[f] = p->field[f];
     k.column = p->column; k.npoint = p->npoint; k.nfield = p->nfield;
     k.ring = p->ring + (size_t)(p->slot % p->nslot) * p->nfield * p->npoint;
-    probe_blocks = (unsigned)((p->npoint * p->nfield + kBlock - 1) / kBlock);
+    probe_blocks = grid_1d(p->npoint * p->nfield, kBlock).x;
   }
   const unsigned blocks = k.col_blocks + probe_blocks;
   if (blocks == 0) return 0;
@@ -240,14 +236,14 @@ int noahmp_hip_history_finish(int n, const noahmp_history_entry* e, void* const*
   static const char* who = "noahmp_hip_history_finish";
   int rc = check_entries(who, n, e);
   if (rc) return rc;
-  if (n > 0 && !fin_flags) { g.last_error = "noahmp_hip_history_finish: fin_flags is required"; return -105; }
+  if (n > 0 && !fin_flags) return refuse(-105, "noahmp_hip_history_finish: fin_flags is required");
   const long ncol = (long)ni * nj;
-  if (ni < 0 || nj < 0 || ncol > 0x7FFFFFFFL) { g.last_error = "noahmp_hip_history_finish: 0 .. 2^31 - 1 columns"; return -105; }
+  if (bad_window(ni, nj)) return refuse(-105, "noahmp_hip_history_finish: 0 .. 2^31 - 1 columns");
   for (int f = 0; f < n; f++)
-    if ((fin_flags[f] & NOAHMP_HIST_FIN_MEAN) && !count) { g.last_error = "noahmp_hip_history_finish: NOAHMP_HIST_FIN_MEAN needs the count plane"; return -105; }
+    if ((fin_flags[f] & NOAHMP_HIST_FIN_MEAN) && !count) return refuse(-105, "noahmp_hip_history_finish: NOAHMP_HIST_FIN_MEAN needs the count plane");
   rc = nmp_host::ensure_init();
   if (rc) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   FinKArgs k;
   memset(&k, 0, sizeof(k));
   for (int f = 0; f < n; f++) {
@@ -255,7 +251,7 @@ int noahmp_hip_history_finish(int n, const noahmp_history_entry* e, void* const*
   }
   k.count = count; k.perm = perm; k.vegtyp = ivgtyp_src; k.iswater = iswater; k.n = n; k.ni = ni; k.nj = nj; k.fill = fill;
   if (ncol > 0 && n > 0)
-    hipLaunchKernelGGL(noahmp_history_finish_kernel, dim3((unsigned)((ncol + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+    hipLaunchKernelGGL(noahmp_history_finish_kernel, grid_1d(ncol, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }

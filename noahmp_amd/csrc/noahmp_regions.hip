@@ -32,7 +32,7 @@
 #include "nmp_engine_host.hpp"
 
 using namespace nmp;
-using nmp_host::g;
+using nmp_host::g, nmp_host::refuse, nmp_host::stream_of, nmp_host::grid_1d;
 
 namespace {
 
@@ -195,8 +195,6 @@ __global__ void __launch_bounds__(kBlock) noahmp_region_upper_kernel(const UpArg
   if (k.acc) k.acc[o] = reg_combine(op, k.acc[o], r);
 }
 
-int refuse(int rc, const char* text) { g.last_error = text; return rc; }
-
 }  // namespace
 
 namespace nmp_host {
@@ -223,20 +221,16 @@ int noahmp_hip_region_plan_size(int ni, int nj, int nregion, int64_t* words) {
 int noahmp_hip_region_plan(const int32_t* region_tile, const float* weight_tile, int ni, int nj, int nregion, const int32_t* inv_perm,
                            int32_t* plan, int64_t plan_words, void* stream) {
   static const char* who = "noahmp_hip_region_plan";
-  char b[200];
   int64_t need_words = 0;
   int rc = noahmp_hip_region_plan_size(ni, nj, nregion, &need_words);
   if (rc) return rc;
   if (!region_tile || !plan) return refuse(-105, "noahmp_hip_region_plan: region_tile and plan are required");
   if ((uintptr_t)plan & 7u) return refuse(-105, "noahmp_hip_region_plan: the plan workspace must be 8-byte aligned");
-  if (plan_words < need_words) {
-    snprintf(b, sizeof b, "%s: the workspace has %lld words, noahmp_hip_region_plan_size asks for %lld", who, (long long)plan_words, (long long)need_words);
-    g.last_error = b;
-    return -105;
-  }
+  if (plan_words < need_words)
+    return refuse(-105, "%s: the workspace has %lld words, noahmp_hip_region_plan_size asks for %lld", who, (long long)plan_words, (long long)need_words);
   rc = nmp_host::ensure_init();
   if (rc) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   const Layout l = layout_of(ni, nj, nregion);
   const long n = l.n;
   std::lock_guard<std::mutex> pk(g_plan_mu);
@@ -254,8 +248,8 @@ int noahmp_hip_region_plan(const int32_t* region_tile, const float* weight_tile,
     if ((rc = nmp_host::ensure_bytes((void**)&sc.keys_in, &sc.keys_in_b, n * 4))) return rc;
     if ((rc = nmp_host::ensure_bytes((void**)&sc.keys_out, &sc.keys_out_b, n * 4))) return rc;
     if ((rc = nmp_host::ensure_bytes((void**)&sc.idx_in, &sc.idx_in_b, n * 4))) return rc;
-    const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(region_key_kernel, dim3(nb), dim3(kBlock), 0, s, region_tile, n, nregion, sc.keys_in, sc.idx_in, hdr);
+    const dim3 nb = grid_1d(n, kBlock);
+    hipLaunchKernelGGL(region_key_kernel, nb, dim3(kBlock), 0, s, region_tile, n, nregion, sc.keys_in, sc.idx_in, hdr);
     int bits = 1;
     while (bits < 32 && (1u << bits) <= (unsigned)nregion) bits++;  // keys are 0 .. nregion
     size_t need = 0;
@@ -263,8 +257,8 @@ int noahmp_hip_region_plan(const int32_t* region_tile, const float* weight_tile,
     if ((rc = nmp_host::ensure_bytes(&sc.tmp, &sc.tmp_b, need))) return rc;
     HIPCHK(rocprim::radix_sort_pairs(sc.tmp, need, sc.keys_in, sc.keys_out, sc.idx_in, tile, (size_t)n, 0, bits, s));   // LSD radix: stable
   }
-  const unsigned rb = (unsigned)((nregion + 1 + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(region_offsets_kernel, dim3(rb), dim3(kBlock), 0, s, sc.keys_out, n, nregion, roff);
+  const dim3 rb = grid_1d(nregion + 1, kBlock);
+  hipLaunchKernelGGL(region_offsets_kernel, rb, dim3(kBlock), 0, s, sc.keys_out, n, nregion, roff);
   auto cnt = rocprim::make_counting_iterator<int>(0);
   for (int level = 1; level <= 2; level++) {
     const int* off = level == 1 ? roff : choff1;
@@ -275,11 +269,11 @@ int noahmp_hip_region_plan(const int32_t* region_tile, const float* weight_tile,
     if ((rc = nmp_host::ensure_bytes(&sc.tmp, &sc.tmp_b, need))) return rc;
     HIPCHK(rocprim::exclusive_scan(sc.tmp, need, in, choff, 0, (size_t)nregion + 1, rocprim::plus<int>(), s));
     const long bound = level == 1 ? l.b1 : l.b2;
-    hipLaunchKernelGGL(region_chunks_kernel, dim3((unsigned)((bound + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, off, choff, nregion, bound,
+    hipLaunchKernelGGL(region_chunks_kernel, grid_1d(bound + 1, kBlock), dim3(kBlock), 0, s, off, choff, nregion, bound,
                        level == 1 ? cstart1 : cstart2, level == 1 ? hdr + H_MAXC1 : (int*)nullptr);
   }
   if (n > 0)
-    hipLaunchKernelGGL(region_members_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, tile, roff, nregion, weight_tile, true,
+    hipLaunchKernelGGL(region_members_kernel, grid_1d(n, kBlock), dim3(kBlock), 0, s, tile, roff, nregion, weight_tile, true,
                        inv_perm, w, pos);
   hipLaunchKernelGGL(region_header_kernel, dim3(1), dim3(1), 0, s, hdr, roff, choff1, choff2, ni, nj, nregion, weight_tile ? 1 : 0);
   HIPCHK(hipGetLastError());
@@ -287,9 +281,7 @@ int noahmp_hip_region_plan(const int32_t* region_tile, const float* weight_tile,
   HIPCHK(hipStreamSynchronize(s));
   if (sc.h_hdr[H_BAD]) {
     hipMemsetAsync(hdr, 0, H_WORDS * sizeof(int), s);
-    snprintf(b, sizeof b, "%s: a cell has a region id >= nregion = %d", who, nregion);
-    g.last_error = b;
-    return -105;
+    return refuse(-105, "%s: a cell has a region id >= nregion = %d", who, nregion);
   }
   PlanInfo pi;
   pi.ni = ni; pi.nj = nj; pi.nregion = nregion; pi.l = l;
@@ -304,11 +296,8 @@ int noahmp_hip_region_plan(const int32_t* region_tile, const float* weight_tile,
 static int find_plan(const char* who, const void* plan, PlanInfo& pi) {
   std::lock_guard<std::mutex> lk(g_mu);
   auto it = g_plans.find(plan);
-  if (!plan || it == g_plans.end()) {
-    char b[200]; snprintf(b, sizeof b, "%s: not a plan noahmp_hip_region_plan has built", who);
-    g.last_error = b;
-    return -105;
-  }
+  if (!plan || it == g_plans.end())
+    return refuse(-105, "%s: not a plan noahmp_hip_region_plan has built", who);
   pi = it->second;
   return 0;
 }
@@ -319,9 +308,9 @@ int noahmp_hip_region_plan_follow(int32_t* plan, const int32_t* inv_perm, void* 
   if (rc) return rc;
   rc = nmp_host::ensure_init();
   if (rc) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   if (pi.nmember > 0)
-    hipLaunchKernelGGL(region_members_kernel, dim3((unsigned)((pi.nmember + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, plan + pi.l.tile,
+    hipLaunchKernelGGL(region_members_kernel, grid_1d(pi.nmember, kBlock), dim3(kBlock), 0, s, plan + pi.l.tile,
                        plan + pi.l.roff, pi.nregion, (const float*)nullptr, false, inv_perm, (float*)nullptr, plan + pi.l.pos);
   HIPCHK(hipGetLastError());
   return 0;
@@ -340,13 +329,12 @@ int noahmp_hip_region_scratch_size(const int32_t* plan, int n, int64_t* bytes) {
 int noahmp_hip_region_step(const int32_t* plan, int n, const noahmp_region_entry* e, const noahmp_step_args* a, double* series, int nslot,
                            int slot, double* acc, void* scratch, void* stream) {
   static const char* who = "noahmp_hip_region_step";
-  char b[200];
-  if (n < 0 || n > kMaxEntries) { snprintf(b, sizeof b, "%s: 0..%d entries per call (n = %d)", who, kMaxEntries, n); g.last_error = b; return -107; }
+  if (n < 0 || n > kMaxEntries) return refuse(-107, "%s: 0..%d entries per call (n = %d)", who, kMaxEntries, n);
   if (n > 0 && !e) return refuse(-105, "noahmp_hip_region_step: entries are NULL");
   for (int f = 0; f < n; f++) {
-    if (e[f].op < NOAHMP_REG_SUM || e[f].op > NOAHMP_REG_MAX) { snprintf(b, sizeof b, "%s: entry %d has op %d (NOAHMP_REG_SUM .. NOAHMP_REG_MAX)", who, f, e[f].op); g.last_error = b; return -105; }
+    if (e[f].op < NOAHMP_REG_SUM || e[f].op > NOAHMP_REG_MAX) return refuse(-105, "%s: entry %d has op %d (NOAHMP_REG_SUM .. NOAHMP_REG_MAX)", who, f, e[f].op);
     if (e[f].nlev < 1 || e[f].nlev > kMaxLevels || e[f].lev < 0 || e[f].lev >= e[f].nlev) {
-      snprintf(b, sizeof b, "%s: entry %d takes level %d of %d (1..%d levels)", who, f, e[f].lev, e[f].nlev, kMaxLevels); g.last_error = b; return -105;
+      return refuse(-105, "%s: entry %d takes level %d of %d (1..%d levels)", who, f, e[f].lev, e[f].nlev, kMaxLevels);
     }
   }
   PlanInfo pi;
@@ -354,17 +342,14 @@ int noahmp_hip_region_step(const int32_t* plan, int n, const noahmp_region_entry
   if (rc) return rc;
   if (!a || !a->xland || !a->xice) return refuse(-105, "noahmp_hip_region_step: the step block and its XLAND / XICE planes are required");
   if (a->ims != a->its || a->ime != a->ite || a->jms != a->jts || a->jme != a->jte) return refuse(-105, "noahmp_hip_region_step: the memory block must be the tile");
-  if (a->ime - a->ims + 1 != pi.ni || a->jme - a->jms + 1 != pi.nj) {
-    snprintf(b, sizeof b, "%s: the block is %d x %d, the plan's tile %d x %d", who, a->ime - a->ims + 1, a->jme - a->jms + 1, pi.ni, pi.nj);
-    g.last_error = b;
-    return -105;
-  }
+  if (a->ime - a->ims + 1 != pi.ni || a->jme - a->jms + 1 != pi.nj)
+    return refuse(-105, "%s: the block is %d x %d, the plan's tile %d x %d", who, a->ime - a->ims + 1, a->jme - a->jms + 1, pi.ni, pi.nj);
   if (!series || nslot < 1 || slot < 0) return refuse(-105, "noahmp_hip_region_step: the series ring is required, with nslot >= 1 and slot >= 0");
   if (!scratch || ((uintptr_t)scratch & 7u)) return refuse(-105, "noahmp_hip_region_step: scratch is required, 8-byte aligned");
   rc = nmp_host::ensure_init();
   if (rc) return rc;
   if (n == 0 || pi.nregion == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   double* p1 = (double*)scratch;
   double* p2 = p1 + (size_t)n * pi.nchunk1;
   if (pi.nchunk1 > 0) {
@@ -379,7 +364,7 @@ int noahmp_hip_region_step(const int32_t* plan, int n, const noahmp_region_entry
     k.xice_thres = a->xice_thres;
     k.out = p1; k.n = n; k.ni = pi.ni; k.nchunk = pi.nchunk1; k.ncol = (long)pi.ni * pi.nj;
     const int per_block = kWaves * kChunksPerWave;
-    hipLaunchKernelGGL(noahmp_region_level1_kernel, dim3((unsigned)((pi.nchunk1 + per_block - 1) / per_block)), dim3(kBlock), 0, s, k);
+    hipLaunchKernelGGL(noahmp_region_level1_kernel, grid_1d(pi.nchunk1, per_block), dim3(kBlock), 0, s, k);
   }
   UpArgs u;
   memset(&u, 0, sizeof u);

@@ -23,7 +23,7 @@
 #include "nmp_engine_host.hpp"
 
 using namespace nmp;
-using nmp_host::g;
+using nmp_host::g, nmp_host::refuse, nmp_host::bad_count, nmp_host::bad_window, nmp_host::stream_of, nmp_host::grid_1d;
 
 namespace {
 
@@ -209,12 +209,9 @@ __global__ void __launch_bounds__(kBlock) noahmp_regrid_plan_kernel(const PlanKA
 }
 
 int check_source(const char* who, const noahmp_regrid_source* src) {
-  char b[200];
-  if (!src) { snprintf(b, sizeof b, "%s: the source grid is NULL", who); g.last_error = b; return -105; }
-  if (src->nx < 2 || src->ny < 2 || (long)src->nx * src->ny > (1L << 30)) {
-    snprintf(b, sizeof b, "%s: the source grid needs nx, ny >= 2 and nx*ny <= 2^30 (nx = %d, ny = %d)", who, src->nx, src->ny);
-    g.last_error = b; return -105;
-  }
+  if (!src) return refuse(-105, "%s: the source grid is NULL", who);
+  if (src->nx < 2 || src->ny < 2 || (long)src->nx * src->ny > (1L << 30))
+    return refuse(-105, "%s: the source grid needs nx, ny >= 2 and nx*ny <= 2^30 (nx = %d, ny = %d)", who, src->nx, src->ny);
   return 0;
 }
 
@@ -229,30 +226,29 @@ namespace {
 // both regrid calls: the checks, then ONE launch (with_met: noahmp_hip_forcing_regrid_met)
 int regrid_call(const char* who, const int32_t* plan, int64_t ncell, const noahmp_regrid_source* src, bool with_met, const noahmp_regrid_met* met,
                 int n, const noahmp_regrid_entry* e, void* stream) {
-  char b[200];
-  if (n < 0 || n > kMaxEntries) { snprintf(b, sizeof b, "%s: 0..%d entries per call (n = %d)", who, kMaxEntries, n); g.last_error = b; return -107; }
+  if (n < 0 || n > kMaxEntries) return refuse(-107, "%s: 0..%d entries per call (n = %d)", who, kMaxEntries, n);
   int rc = check_source(who, src);
   if (rc) return rc;
-  if (ncell < 0 || ncell > 0x7FFFFFFFL) { snprintf(b, sizeof b, "%s: 0 .. 2^31 - 1 columns", who); g.last_error = b; return -105; }
-  if (!plan) { snprintf(b, sizeof b, "%s: the plan is NULL", who); g.last_error = b; return -105; }
-  if (n > 0 && !e) { snprintf(b, sizeof b, "%s: entries are NULL", who); g.last_error = b; return -105; }
+  if (bad_count(ncell)) return refuse(-105, "%s: 0 .. 2^31 - 1 columns", who);
+  if (!plan) return refuse(-105, "%s: the plan is NULL", who);
+  if (n > 0 && !e) return refuse(-105, "%s: entries are NULL", who);
   for (int f = 0; f < n; f++) {
     if (e[f].mode < NOAHMP_REGRID_BILINEAR || e[f].mode > NOAHMP_REGRID_NEAREST) {
-      snprintf(b, sizeof b, "%s: entry %d has mode %d (NOAHMP_REGRID_BILINEAR, NOAHMP_REGRID_NEAREST)", who, f, e[f].mode); g.last_error = b; return -105;
+      return refuse(-105, "%s: entry %d has mode %d (NOAHMP_REGRID_BILINEAR, NOAHMP_REGRID_NEAREST)", who, f, e[f].mode);
     }
-    if (!e[f].src || !e[f].dst) { snprintf(b, sizeof b, "%s: entry %d has a NULL plane", who, f); g.last_error = b; return -105; }
+    if (!e[f].src || !e[f].dst) return refuse(-105, "%s: entry %d has a NULL plane", who, f);
   }
   if (with_met) {
-    if (!met) { snprintf(b, sizeof b, "%s: met is NULL", who); g.last_error = b; return -105; }
+    if (!met) return refuse(-105, "%s: met is NULL", who);
     if (!met->src_t || !met->src_p || !met->src_q || !met->dst_t || !met->dst_p || !met->dst_q || !met->dz) {
-      snprintf(b, sizeof b, "%s: met needs src_t, src_p, src_q, dst_t, dst_p, dst_q and dz", who); g.last_error = b; return -105;
+      return refuse(-105, "%s: met needs src_t, src_p, src_q, dst_t, dst_p, dst_q and dz", who);
     }
-    if (met->src_lw && !met->dst_lw) { snprintf(b, sizeof b, "%s: met has src_lw but no dst_lw", who); g.last_error = b; return -105; }
+    if (met->src_lw && !met->dst_lw) return refuse(-105, "%s: met has src_lw but no dst_lw", who);
   }
   rc = nmp_host::ensure_init();
   if (rc) return rc;
   if ((n == 0 && !with_met) || ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   RegridMetKArgs k;                      // the MET = false kernels receive its RegridKArgs part
   memset(&k, 0, sizeof(k));
   bool vec = aligned16(plan) && (ncell & 3) == 0;
@@ -272,13 +268,13 @@ int regrid_call(const char* who, const int32_t* plan, int64_t ncell, const noahm
   for (int q = 0; q < 4; q++) k.w[q] = (const float*)(plan + (2 + q) * ncell);
   k.n = n; k.nx = src->nx; k.nxny = src->nx * src->ny; k.periodic = src->periodic_x ? 1 : 0; k.ncell = ncell;
   const long nthread = vec ? ncell / 4 : ncell;
-  const unsigned blocks = (unsigned)((nthread + kBlock - 1) / kBlock);
+  const dim3 blocks = grid_1d(nthread, kBlock);
   const RegridKArgs& kk = k;
   if (with_met) {
-    hipLaunchKernelGGL((noahmp_regrid_kernel<false, true>), dim3(blocks), dim3(kBlock), 0, s, k);
+    hipLaunchKernelGGL((noahmp_regrid_kernel<false, true>), blocks, dim3(kBlock), 0, s, k);
   } else {
-    if (vec) hipLaunchKernelGGL((noahmp_regrid_kernel<true, false>), dim3(blocks), dim3(kBlock), 0, s, kk);
-    else hipLaunchKernelGGL((noahmp_regrid_kernel<false, false>), dim3(blocks), dim3(kBlock), 0, s, kk);
+    if (vec) hipLaunchKernelGGL((noahmp_regrid_kernel<true, false>), blocks, dim3(kBlock), 0, s, kk);
+    else hipLaunchKernelGGL((noahmp_regrid_kernel<false, false>), blocks, dim3(kBlock), 0, s, kk);
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -296,10 +292,7 @@ void regrid_finalize() {
 extern "C" {
 
 int noahmp_hip_regrid_plan_size(int ni, int nj, int64_t* words) {
-  if (ni < 0 || nj < 0 || (long)ni * nj > 0x7FFFFFFFL || !words) {
-    g.last_error = "noahmp_hip_regrid_plan_size: 0 .. 2^31 - 1 cells and a place for the size";
-    return -105;
-  }
+  if (bad_window(ni, nj) || !words) return refuse(-105, "noahmp_hip_regrid_plan_size: 0 .. 2^31 - 1 cells and a place for the size");
   *words = 6 * (int64_t)ni * nj + 1;
   return 0;
 }
@@ -308,21 +301,18 @@ int noahmp_hip_regrid_plan_latlon(const float* xlat, const float* xlon, int ni, 
                                   const uint8_t* valid_src, int search_radius, int32_t* plan, int64_t plan_words, int32_t* unfilled,
                                   void* stream) {
   static const char* who = "noahmp_hip_regrid_plan_latlon";
-  char b[200];
   int rc = check_source(who, src);
   if (rc) return rc;
-  if (!(src->dlon > 0.0) || !(src->dlat != 0.0)) { snprintf(b, sizeof b, "%s: dlon > 0 and dlat != 0 are required", who); g.last_error = b; return -105; }
-  if (search_radius < 0 || search_radius > kMaxRadius) { snprintf(b, sizeof b, "%s: search_radius 0..%d (%d)", who, kMaxRadius, search_radius); g.last_error = b; return -105; }
+  if (!(src->dlon > 0.0) || !(src->dlat != 0.0)) return refuse(-105, "%s: dlon > 0 and dlat != 0 are required", who);
+  if (search_radius < 0 || search_radius > kMaxRadius) return refuse(-105, "%s: search_radius 0..%d (%d)", who, kMaxRadius, search_radius);
   const long ncell = (long)ni * nj;
-  if (ni < 0 || nj < 0 || ncell > 0x7FFFFFFFL) { snprintf(b, sizeof b, "%s: 0 .. 2^31 - 1 cells", who); g.last_error = b; return -105; }
-  if (!plan || (ncell > 0 && (!xlat || !xlon))) { snprintf(b, sizeof b, "%s: xlat, xlon and plan are required", who); g.last_error = b; return -105; }
-  if (plan_words < 6 * (int64_t)ncell + 1) {
-    snprintf(b, sizeof b, "%s: the workspace has %lld words, noahmp_hip_regrid_plan_size asks for %lld", who, (long long)plan_words, (long long)(6 * (int64_t)ncell + 1));
-    g.last_error = b; return -105;
-  }
+  if (bad_window(ni, nj)) return refuse(-105, "%s: 0 .. 2^31 - 1 cells", who);
+  if (!plan || (ncell > 0 && (!xlat || !xlon))) return refuse(-105, "%s: xlat, xlon and plan are required", who);
+  if (plan_words < 6 * (int64_t)ncell + 1)
+    return refuse(-105, "%s: the workspace has %lld words, noahmp_hip_regrid_plan_size asks for %lld", who, (long long)plan_words, (long long)(6 * (int64_t)ncell + 1));
   rc = nmp_host::ensure_init();
   if (rc) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   if (!h_unfilled) HIPCHK(hipHostMalloc((void**)&h_unfilled, sizeof(int), hipHostMallocDefault));
   PlanKArgs k;
   memset(&k, 0, sizeof(k));
@@ -330,7 +320,7 @@ int noahmp_hip_regrid_plan_latlon(const float* xlat, const float* xlon, int ni, 
   k.nx = src->nx; k.ny = src->ny; k.periodic = src->periodic_x ? 1 : 0; k.radius = search_radius;
   k.lon0 = src->lon0; k.lat0 = src->lat0; k.dlon = src->dlon; k.dlat = src->dlat;
   HIPCHK(hipMemsetAsync(k.unfilled, 0, sizeof(int), s));
-  if (ncell > 0) hipLaunchKernelGGL(noahmp_regrid_plan_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  if (ncell > 0) hipLaunchKernelGGL(noahmp_regrid_plan_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h_unfilled, k.unfilled, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));

@@ -31,7 +31,7 @@
 #include "nmp_engine_host.hpp"
 
 using namespace nmp;
-using nmp_host::g;
+using nmp_host::g, nmp_host::refuse, nmp_host::stream_of, nmp_host::grid_1d;
 using tree::kChunk; using tree::kBlock; using tree::kWaves;
 using tree::region_offsets_kernel; using tree::region_chunks_kernel; using tree::ChunkCount; using tree::wave_fold;
 
@@ -325,26 +325,18 @@ __global__ void __launch_bounds__(kBlock) noahmp_regrid_conserve_apply_kernel(co
   }
 }
 
-int refuse(int rc, const char* text) { g.last_error = text; return rc; }
-
 int check_source(const char* who, const noahmp_regrid_source* src) {
-  char b[200];
-  if (!src) { snprintf(b, sizeof b, "%s: the source grid is NULL", who); g.last_error = b; return -105; }
-  if (src->nx < 2 || src->ny < 2 || (long)src->nx * src->ny > kMaxCells) {
-    snprintf(b, sizeof b, "%s: the source grid needs nx, ny >= 2 and nx*ny <= 2^24 (nx = %d, ny = %d)", who, src->nx, src->ny);
-    g.last_error = b; return -105;
-  }
+  if (!src) return refuse(-105, "%s: the source grid is NULL", who);
+  if (src->nx < 2 || src->ny < 2 || (long)src->nx * src->ny > kMaxCells)
+    return refuse(-105, "%s: the source grid needs nx, ny >= 2 and nx*ny <= 2^24 (nx = %d, ny = %d)", who, src->nx, src->ny);
   return 0;
 }
 
 int find_plan(const char* who, const void* plan, PlanInfo& pi) {
   std::lock_guard<std::mutex> lk(g_mu);
   auto it = g_plans.find(plan);
-  if (!plan || it == g_plans.end()) {
-    char b[200]; snprintf(b, sizeof b, "%s: not a plan noahmp_hip_regrid_conserve_plan has built", who);
-    g.last_error = b;
-    return -105;
-  }
+  if (!plan || it == g_plans.end())
+    return refuse(-105, "%s: not a plan noahmp_hip_regrid_conserve_plan has built", who);
   pi = it->second;
   return 0;
 }
@@ -395,21 +387,17 @@ int noahmp_hip_regrid_conserve_plan(const int32_t* regrid_plan, int ni, int nj, 
                                     const int32_t* dst_index, int domain_edges, int32_t* cplan, int64_t cplan_words, int32_t* clipped,
                                     void* stream) {
   static const char* who = "noahmp_hip_regrid_conserve_plan";
-  char b[200];
   int64_t need_words = 0;
   int rc = noahmp_hip_regrid_conserve_plan_size(ni, nj, src, &need_words);
   if (rc) return rc;
   if (!regrid_plan || !cplan) return refuse(-105, "noahmp_hip_regrid_conserve_plan: regrid_plan and cplan are required");
   if ((uintptr_t)cplan & 7u) return refuse(-105, "noahmp_hip_regrid_conserve_plan: the plan workspace must be 8-byte aligned");
   if (domain_edges < 0 || domain_edges > 15) return refuse(-105, "noahmp_hip_regrid_conserve_plan: domain_edges is a set of NOAHMP_REGRID_EDGE_* bits (0..15)");
-  if (cplan_words < need_words) {
-    snprintf(b, sizeof b, "%s: the workspace has %lld words, noahmp_hip_regrid_conserve_plan_size asks for %lld", who, (long long)cplan_words, (long long)need_words);
-    g.last_error = b;
-    return -105;
-  }
+  if (cplan_words < need_words)
+    return refuse(-105, "%s: the workspace has %lld words, noahmp_hip_regrid_conserve_plan_size asks for %lld", who, (long long)cplan_words, (long long)need_words);
   rc = nmp_host::ensure_init();
   if (rc) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   const int ngroup = src->nx * src->ny;
   const Layout l = layout_of(ni, nj, ngroup);
   const long n = l.n;
@@ -436,7 +424,7 @@ int noahmp_hip_regrid_conserve_plan(const int32_t* regrid_plan, int ni, int nj, 
     for (int q = 0; q < 4; q++) k.w[q] = (const float*)(regrid_plan + (2 + q) * n);
     k.area = area; k.dst_index = dst_index; k.keys = sc.keys_in; k.idx = sc.idx_in; k.group = group; k.gflag = gflag; k.hdr = hdr;
     k.n = n; k.ni = ni; k.nj = nj; k.nx = src->nx; k.nxny = ngroup; k.periodic = src->periodic_x ? 1 : 0; k.edges = domain_edges;
-    hipLaunchKernelGGL(conserve_key_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+    hipLaunchKernelGGL(conserve_key_kernel, grid_1d(n, kBlock), dim3(kBlock), 0, s, k);
     int bits = 1;
     while (bits < 32 && (1u << bits) <= (unsigned)ngroup) bits++;   // keys are 0 .. ngroup
     size_t need = 0;
@@ -444,7 +432,7 @@ int noahmp_hip_regrid_conserve_plan(const int32_t* regrid_plan, int ni, int nj, 
     if ((rc = nmp_host::ensure_bytes(&sc.tmp, &sc.tmp_b, need))) return rc;
     HIPCHK(rocprim::radix_sort_pairs(sc.tmp, need, sc.keys_in, sc.keys_out, sc.idx_in, member, (size_t)n, 0, bits, s));   // LSD radix: stable
   }
-  hipLaunchKernelGGL(region_offsets_kernel, dim3((unsigned)((ngroup + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, sc.keys_out, n, ngroup, goff);
+  hipLaunchKernelGGL(region_offsets_kernel, grid_1d(ngroup + 1, kBlock), dim3(kBlock), 0, s, sc.keys_out, n, ngroup, goff);
   auto cnt = rocprim::make_counting_iterator<int>(0);
   for (int level = 1; level <= 2; level++) {
     const int* off = level == 1 ? goff : choff1;
@@ -455,21 +443,19 @@ int noahmp_hip_regrid_conserve_plan(const int32_t* regrid_plan, int ni, int nj, 
     if ((rc = nmp_host::ensure_bytes(&sc.tmp, &sc.tmp_b, need))) return rc;
     HIPCHK(rocprim::exclusive_scan(sc.tmp, need, in, choff, 0, (size_t)ngroup + 1, rocprim::plus<int>(), s));
     const long bound = level == 1 ? l.b1 : l.b2;
-    hipLaunchKernelGGL(region_chunks_kernel, dim3((unsigned)((bound + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, off, choff, ngroup, bound,
+    hipLaunchKernelGGL(region_chunks_kernel, grid_1d(bound + 1, kBlock), dim3(kBlock), 0, s, off, choff, ngroup, bound,
                        level == 1 ? cstart1 : cstart2, level == 1 ? hdr + H_MAXC1 : (int*)nullptr);
   }
   if (n > 0 && area)
-    hipLaunchKernelGGL(conserve_members_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, member, goff, ngroup, area, aw);
-  hipLaunchKernelGGL(conserve_clipped_kernel, dim3((unsigned)((ngroup + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, gflag, ngroup, hdr);
+    hipLaunchKernelGGL(conserve_members_kernel, grid_1d(n, kBlock), dim3(kBlock), 0, s, member, goff, ngroup, area, aw);
+  hipLaunchKernelGGL(conserve_clipped_kernel, grid_1d(ngroup, kBlock), dim3(kBlock), 0, s, gflag, ngroup, hdr);
   hipLaunchKernelGGL(conserve_header_kernel, dim3(1), dim3(1), 0, s, hdr, goff, choff1, choff2, ni, nj, ngroup, area ? 1 : 0);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(sc.h_hdr, hdr, H_WORDS * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (sc.h_hdr[H_BAD]) {
     hipMemsetAsync(hdr, 0, H_WORDS * sizeof(int), s);
-    snprintf(b, sizeof b, "%s: the area of a member is not finite and > 0", who);
-    g.last_error = b;
-    return -105;
+    return refuse(-105, "%s: the area of a member is not finite and > 0", who);
   }
   PlanInfo pi;
   pi.ni = ni; pi.nj = nj; pi.nx = src->nx; pi.ny = src->ny; pi.periodic = src->periodic_x ? 1 : 0; pi.l = l;
@@ -486,7 +472,7 @@ int noahmp_hip_regrid_conserve_plan(const int32_t* regrid_plan, int ni, int nj, 
     k.cstart = cstart1; k.member = member; k.aw = pi.has_area ? aw : nullptr; k.out = p1;
     k.n = 1; k.nchunk = pi.nchunk1; k.area_only = 1; k.ncell = n;
     const int per_block = kWaves * kChunksPerWave;
-    hipLaunchKernelGGL(noahmp_regrid_conserve_level1_kernel, dim3((unsigned)((pi.nchunk1 + per_block - 1) / per_block)), dim3(kBlock), 0, s, k);
+    hipLaunchKernelGGL(noahmp_regrid_conserve_level1_kernel, grid_1d(pi.nchunk1, per_block), dim3(kBlock), 0, s, k);
   }
   UpArgs u;
   memset(&u, 0, sizeof u);
@@ -514,28 +500,25 @@ int noahmp_hip_forcing_regrid_conserve(const int32_t* cplan, const int32_t* regr
                                        const int32_t* dst_index, int64_t ndst, int n, const noahmp_regrid_conserve_entry* e,
                                        double* group_sum, void* scratch, void* stream) {
   static const char* who = "noahmp_hip_forcing_regrid_conserve";
-  char b[200];
-  if (n < 1 || n > kMaxEntries) { snprintf(b, sizeof b, "%s: 1..%d entries per call (n = %d)", who, kMaxEntries, n); g.last_error = b; return -107; }
+  if (n < 1 || n > kMaxEntries) return refuse(-107, "%s: 1..%d entries per call (n = %d)", who, kMaxEntries, n);
   int rc = check_source(who, src);
   if (rc) return rc;
   if (!regrid_plan) return refuse(-105, "noahmp_hip_forcing_regrid_conserve: the regrid plan is NULL");
   if (!e) return refuse(-105, "noahmp_hip_forcing_regrid_conserve: entries are NULL");
   for (int f = 0; f < n; f++)
-    if (!e[f].src || !e[f].dst) { snprintf(b, sizeof b, "%s: entry %d has a NULL plane", who, f); g.last_error = b; return -105; }
+    if (!e[f].src || !e[f].dst) return refuse(-105, "%s: entry %d has a NULL plane", who, f);
   if (ndst < 0) return refuse(-105, "noahmp_hip_forcing_regrid_conserve: ndst < 0");
   PlanInfo pi;
   rc = find_plan(who, cplan, pi);
   if (rc) return rc;
-  if (src->nx != pi.nx || src->ny != pi.ny || (src->periodic_x ? 1 : 0) != pi.periodic) {
-    snprintf(b, sizeof b, "%s: the source grid is %d x %d, the plan's %d x %d (or periodic_x differs)", who, src->nx, src->ny, pi.nx, pi.ny);
-    g.last_error = b; return -105;
-  }
+  if (src->nx != pi.nx || src->ny != pi.ny || (src->periodic_x ? 1 : 0) != pi.periodic)
+    return refuse(-105, "%s: the source grid is %d x %d, the plan's %d x %d (or periodic_x differs)", who, src->nx, src->ny, pi.nx, pi.ny);
   if (!scratch || ((uintptr_t)scratch & 7u)) return refuse(-105, "noahmp_hip_forcing_regrid_conserve: scratch is required, 8-byte aligned");
   rc = nmp_host::ensure_init();
   if (rc) return rc;
   const long ncell = pi.l.n;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   const int ngroup = (int)pi.l.ngroup;
   double* p1 = (double*)scratch;
   double* p2 = p1 + (size_t)n * pi.nchunk1;
@@ -552,7 +535,7 @@ int noahmp_hip_forcing_regrid_conserve(const int32_t* cplan, const int32_t* regr
     for (int q = 0; q < 4; q++) k.w[q] = wp[q];
     k.out = p1; k.n = n; k.nx = pi.nx; k.nxny = ngroup; k.periodic = pi.periodic; k.nchunk = pi.nchunk1; k.ncell = ncell;
     const int per_block = kWaves * kChunksPerWave;
-    hipLaunchKernelGGL(noahmp_regrid_conserve_level1_kernel, dim3((unsigned)((pi.nchunk1 + per_block - 1) / per_block)), dim3(kBlock), 0, s, k);
+    hipLaunchKernelGGL(noahmp_regrid_conserve_level1_kernel, grid_1d(pi.nchunk1, per_block), dim3(kBlock), 0, s, k);
   }
   UpArgs u;
   memset(&u, 0, sizeof u);
@@ -565,7 +548,7 @@ int noahmp_hip_forcing_regrid_conserve(const int32_t* cplan, const int32_t* regr
   a.group = cplan + pi.l.group; a.dst_index = dst_index; a.base = regrid_plan;
   for (int q = 0; q < 4; q++) a.w[q] = wp[q];
   a.res = res; a.n = n; a.nx = pi.nx; a.nxny = ngroup; a.periodic = pi.periodic; a.ngroup = ngroup; a.ncell = ncell; a.ndst = ndst;
-  hipLaunchKernelGGL(noahmp_regrid_conserve_apply_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(noahmp_regrid_conserve_apply_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, a);
   HIPCHK(hipGetLastError());
   return 0;
 }

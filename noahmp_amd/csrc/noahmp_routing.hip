@@ -23,7 +23,7 @@
 #endif
 
 using namespace nmp;
-using nmp_host::g;
+using nmp_host::g, nmp_host::refuse, nmp_host::bad_count, nmp_host::bad_window, nmp_host::bad_spacing, nmp_host::stream_of, nmp_host::grid_1d;
 
 namespace {
 
@@ -80,18 +80,7 @@ __global__ void __launch_bounds__(kBlock) noahmp_route_runoff_kernel(const Route
   route_cell<NMP_ROUTE_LOAD_ALL != 0>(k.r, i, j);
 }
 
-int refuse(const char* call, const char* what) {
-  char b[240];
-  snprintf(b, sizeof b, "%s: %s", call, what);
-  g.last_error = b;
-  return -105;
-}
-
-bool bad_window(int ni, int nj) { return ni < 0 || nj < 0 || (int64_t)ni * (int64_t)nj > 0x7FFFFFFFL; }
-
 const char* kWindowText = "window: ni, nj >= 0 and ni*nj <= 2^31 - 1";
-
-dim3 grid_of(unsigned ncell) { return dim3((ncell + kBlock - 1) / kBlock); }
 
 }  // namespace
 
@@ -99,38 +88,38 @@ extern "C" {
 
 int noahmp_hip_flow_terrain(const noahmp_flow_terrain* ft, void* stream) {
   const char* me = "noahmp_hip_flow_terrain";
-  if (!ft) return refuse(me, "the argument block is NULL");
-  if (!ft->height || !ft->dir) return refuse(me, "height and dir are required");
-  if (bad_window(ft->ni, ft->nj)) return refuse(me, kWindowText);
-  if (!(isfinite(ft->dx) && ft->dx > 0.f && isfinite(ft->dy) && ft->dy > 0.f)) return refuse(me, "dx and dy must be finite and > 0");
+  if (!ft) return refuse(-105, "%s: the argument block is NULL", me);
+  if (!ft->height || !ft->dir) return refuse(-105, "%s: height and dir are required", me);
+  if (bad_window(ft->ni, ft->nj)) return refuse(-105, "%s: %s", me, kWindowText);
+  if (bad_spacing(ft->dx, ft->dy)) return refuse(-105, "%s: dx and dy must be finite and > 0", me);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   const unsigned ncell = (unsigned)ft->ni * (unsigned)ft->nj;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   FlowTerrainKArgs k;
   memset(&k, 0, sizeof(k));
   k.height = ft->height; k.dir = ft->dir; k.ncell = ncell;
   k.p = flow_params(ft->ni, ft->nj, ft->dx, ft->dy);
-  hipLaunchKernelGGL(noahmp_flow_terrain_kernel, grid_of(ncell), dim3(kBlock), 0, s, k);
+  hipLaunchKernelGGL(noahmp_flow_terrain_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 int noahmp_hip_flow_inmask(const uint8_t* dir, uint8_t* inmask, int32_t ni, int32_t nj, void* stream) {
   const char* me = "noahmp_hip_flow_inmask";
-  if (!dir || !inmask) return refuse(me, "dir and inmask are required");
-  if (dir == inmask) return refuse(me, "dir and inmask must be different planes (a cell reads its neighbours' dir)");
-  if (bad_window(ni, nj)) return refuse(me, kWindowText);
+  if (!dir || !inmask) return refuse(-105, "%s: dir and inmask are required", me);
+  if (dir == inmask) return refuse(-105, "%s: dir and inmask must be different planes (a cell reads its neighbours' dir)", me);
+  if (bad_window(ni, nj)) return refuse(-105, "%s: %s", me, kWindowText);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   const unsigned ncell = (unsigned)ni * (unsigned)nj;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   FlowInmaskKArgs k;
   memset(&k, 0, sizeof(k));
   k.dir = dir; k.inmask = inmask; k.ncell = ncell; k.ni = ni; k.nj = nj;
-  hipLaunchKernelGGL(noahmp_flow_inmask_kernel, grid_of(ncell), dim3(kBlock), 0, s, k);
+  hipLaunchKernelGGL(noahmp_flow_inmask_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -138,42 +127,42 @@ int noahmp_hip_flow_inmask(const uint8_t* dir, uint8_t* inmask, int32_t ni, int3
 int noahmp_hip_flow_accumulate(const uint8_t* inmask, const uint32_t* acc_old, uint32_t* acc_new, uint32_t* changed, int32_t ni, int32_t nj,
                                void* stream) {
   const char* me = "noahmp_hip_flow_accumulate";
-  if (!inmask || !acc_old || !acc_new || !changed) return refuse(me, "inmask, acc_old, acc_new and changed are required");
-  if (acc_old == acc_new) return refuse(me, "acc_old and acc_new must be different planes (a Jacobi pass)");
-  if (bad_window(ni, nj)) return refuse(me, kWindowText);
+  if (!inmask || !acc_old || !acc_new || !changed) return refuse(-105, "%s: inmask, acc_old, acc_new and changed are required", me);
+  if (acc_old == acc_new) return refuse(-105, "%s: acc_old and acc_new must be different planes (a Jacobi pass)", me);
+  if (bad_window(ni, nj)) return refuse(-105, "%s: %s", me, kWindowText);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   const unsigned ncell = (unsigned)ni * (unsigned)nj;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   FlowAccKArgs k;
   memset(&k, 0, sizeof(k));
   k.inmask = inmask; k.acc_old = acc_old; k.acc_new = acc_new; k.changed = changed; k.ncell = ncell; k.ni = ni; k.nj = nj;
-  hipLaunchKernelGGL(noahmp_flow_accumulate_kernel, grid_of(ncell), dim3(kBlock), 0, s, k);
+  hipLaunchKernelGGL(noahmp_flow_accumulate_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 int noahmp_hip_route_runoff(const noahmp_route* r, int64_t ncol, void* stream) {
   const char* me = "noahmp_hip_route_runoff";
-  if (!r) return refuse(me, "the argument block is NULL");
+  if (!r) return refuse(-105, "%s: the argument block is NULL", me);
   if (!r->inmask || !r->col_index || !r->area || !r->release || !r->storage || !r->out_old || !r->out_new || !r->runoff_a)
-    return refuse(me, "inmask, col_index, area, release, storage, out_old, out_new and runoff_a are required");
-  if (r->out_old == r->out_new) return refuse(me, "out_old and out_new must be different planes (a cell reads its neighbours' out_old)");
-  if (bad_window(r->ni, r->nj)) return refuse(me, kWindowText);
-  if (ncol < 0 || ncol > 0x7FFFFFFFL) return refuse(me, "ncol: 0 .. 2^31 - 1 columns");
+    return refuse(-105, "%s: inmask, col_index, area, release, storage, out_old, out_new and runoff_a are required", me);
+  if (r->out_old == r->out_new) return refuse(-105, "%s: out_old and out_new must be different planes (a cell reads its neighbours' out_old)", me);
+  if (bad_window(r->ni, r->nj)) return refuse(-105, "%s: %s", me, kWindowText);
+  if (bad_count(ncol)) return refuse(-105, "%s: ncol: 0 .. 2^31 - 1 columns", me);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   const unsigned ncell = (unsigned)r->ni * (unsigned)r->nj;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   RouteKArgs k;
   memset(&k, 0, sizeof(k));
   k.r.inmask = r->inmask; k.r.col_index = r->col_index; k.r.area = r->area; k.r.release = r->release; k.r.storage = r->storage;
   k.r.out_old = r->out_old; k.r.out_new = r->out_new; k.r.runoff_a = r->runoff_a; k.r.runoff_b = r->runoff_b; k.r.scale = r->scale;
   k.r.ni = r->ni; k.r.nj = r->nj; k.r.ncol = (long)ncol;
   k.ncell = ncell;
-  hipLaunchKernelGGL(noahmp_route_runoff_kernel, grid_of(ncell), dim3(kBlock), 0, s, k);
+  hipLaunchKernelGGL(noahmp_route_runoff_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }

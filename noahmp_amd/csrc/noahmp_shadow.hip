@@ -22,9 +22,11 @@
 #include "noahmp_hip.h"
 #include "nmp_dev_shadow.hpp"
 #include "nmp_engine_host.hpp"
+#include "nmp_forcing_host.hpp"
 
 using namespace nmp;
-using nmp_host::g;
+using nmp_host::g, nmp_host::refuse, nmp_host::bad_count, nmp_host::bad_window, nmp_host::bad_spacing, nmp_host::stream_of, nmp_host::grid_1d,
+    nmp_host::sun_of;
 
 #ifndef NMP_SHADOW_INFLIGHT
 #define NMP_SHADOW_INFLIGHT 1
@@ -57,43 +59,25 @@ __global__ void __launch_bounds__(kBlock) noahmp_shadow_kernel(const ShadowKArgs
   k.lit[d] = shadow_lit(shadow_cell<kInFlight>(k.p, k.height, lat, lon, ca, sa, i, j));
 }
 
-// what fill_forcing_args makes of a time (noahmp_forcing.hip), as noahmp_shortwave.hip makes it for the shortwave calls
-SunTime sun_of(const noahmp_sun_time& t) {
-  SunTime s;
-  noahmp_hip_declination(t.iday, t.ihour, &s.sin_declin, &s.cos_declin);
-  s.hour_utc = (float)t.ihour + (float)t.iminute / 60.0f + (float)t.isecond / 3600.0f;
-  return s;
-}
-
-int refuse(const char* what) {
-  char b[240];
-  snprintf(b, sizeof b, "noahmp_hip_forcing_shadow: %s", what);
-  g.last_error = b;
-  return -105;
-}
-
 }  // namespace
 
 extern "C" {
 
 int noahmp_hip_forcing_shadow(const noahmp_shadow* sh, int64_t ndst, const noahmp_sun_time* now, void* stream) {
-  if (!sh) return refuse("the argument block is NULL");
-  if (!now) return refuse("now is NULL");
-  if (!sh->height || !sh->xlat || !sh->lon || !sh->lit) return refuse("height, xlat, lon and lit are required");
-  if ((sh->cosalpha != nullptr) != (sh->sinalpha != nullptr)) return refuse("cosalpha and sinalpha go together: both or none");
-  if (sh->ni < 0 || sh->nj < 0 || (int64_t)sh->ni * (int64_t)sh->nj > 0x7FFFFFFFL) return refuse("window: ni, nj >= 0 and ni*nj <= 2^31 - 1");
-  if (sh->nstep < 1 || sh->nstep > kMaxStep) {
-    char b[120];
-    snprintf(b, sizeof b, "nstep %d (1 .. %d cells)", sh->nstep, kMaxStep);
-    return refuse(b);
-  }
-  if (!(isfinite(sh->dx) && sh->dx > 0.f && isfinite(sh->dy) && sh->dy > 0.f)) return refuse("dx and dy must be finite and > 0");
-  if (ndst < 0 || ndst > 0x7FFFFFFFL) return refuse("ndst: 0 .. 2^31 - 1");
+  static const char* who = "noahmp_hip_forcing_shadow";
+  if (!sh) return refuse(-105, "%s: the argument block is NULL", who);
+  if (!now) return refuse(-105, "%s: now is NULL", who);
+  if (!sh->height || !sh->xlat || !sh->lon || !sh->lit) return refuse(-105, "%s: height, xlat, lon and lit are required", who);
+  if ((sh->cosalpha != nullptr) != (sh->sinalpha != nullptr)) return refuse(-105, "%s: cosalpha and sinalpha go together: both or none", who);
+  if (bad_window(sh->ni, sh->nj)) return refuse(-105, "%s: window: ni, nj >= 0 and ni*nj <= 2^31 - 1", who);
+  if (sh->nstep < 1 || sh->nstep > kMaxStep) return refuse(-105, "%s: nstep %d (1 .. %d cells)", who, sh->nstep, kMaxStep);
+  if (bad_spacing(sh->dx, sh->dy)) return refuse(-105, "%s: dx and dy must be finite and > 0", who);
+  if (bad_count(ndst)) return refuse(-105, "%s: ndst: 0 .. 2^31 - 1", who);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   const long ncell = (long)sh->ni * sh->nj;
   if (ndst == 0 || ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   ShadowKArgs k;
   memset(&k, 0, sizeof(k));
   k.height = sh->height; k.xlat = sh->xlat; k.lon = sh->lon; k.cosalpha = sh->cosalpha; k.sinalpha = sh->sinalpha;
@@ -101,7 +85,7 @@ int noahmp_hip_forcing_shadow(const noahmp_shadow* sh, int64_t ndst, const noahm
   k.p.now = sun_of(*now);
   k.p.ni = sh->ni; k.p.nj = sh->nj; k.p.nstep = sh->nstep; k.p.has_rot = sh->cosalpha ? 1 : 0;
   k.p.dx = sh->dx; k.p.dy = sh->dy; k.p.mu_min = sh->mu_min; k.p.height_max = sh->height_max;
-  hipLaunchKernelGGL(noahmp_shadow_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  hipLaunchKernelGGL(noahmp_shadow_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -19,9 +19,10 @@
 #include "noahmp_hip.h"
 #include "nmp_dev_shortwave.hpp"
 #include "nmp_engine_host.hpp"
+#include "nmp_forcing_host.hpp"
 
 using namespace nmp;
-using nmp_host::g;
+using nmp_host::g, nmp_host::refuse, nmp_host::bad_count, nmp_host::stream_of, nmp_host::grid_1d, nmp_host::sun_of;
 
 namespace {
 
@@ -140,39 +141,21 @@ __global__ void __launch_bounds__(kBlock) noahmp_radiation_sky_kernel(const SwKA
 
 inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }      // NULL counts as aligned: the plane is not read
 
-// what fill_forcing_args makes of a time (noahmp_forcing.hip): the declination with the host's libm, hour_utc left to right (hdrv:856)
-SunTime sun_of(const noahmp_sun_time& t) {
-  SunTime s;
-  noahmp_hip_declination(t.iday, t.ihour, &s.sin_declin, &s.cos_declin);
-  s.hour_utc = (float)t.ihour + (float)t.iminute / 60.0f + (float)t.isecond / 3600.0f;
-  return s;
-}
-
-int refuse(int rc, const char* who, const char* what) {
-  char b[240];
-  snprintf(b, sizeof b, "%s: %s", who, what);
-  g.last_error = b;
-  return rc;
-}
-
 // the checks of both shortwave calls and their kernel arguments; 0, or the refusal
 int sw_prepare(const char* who, const noahmp_shortwave* sw, int64_t ncell, const noahmp_sun_time* now, SwKArgs* out) {
-  if (!sw) return refuse(-105, who, "the argument block is NULL");
-  if (!now) return refuse(-105, who, "now is NULL");
-  if (sw->mode != NOAHMP_SW_LINEAR && sw->mode != NOAHMP_SW_ZENITH) {
-    char b[120];
-    snprintf(b, sizeof b, "mode %d (NOAHMP_SW_LINEAR, NOAHMP_SW_ZENITH)", sw->mode);
-    return refuse(-105, who, b);
-  }
-  if (ncell < 0 || ncell > 0x7FFFFFFFL) return refuse(-105, who, "0 .. 2^31 - 1 columns");
-  if (!sw->sw_a || !sw->xlat || !sw->lon || !sw->swdown) return refuse(-105, who, "sw_a, xlat, lon and swdown are required");
+  if (!sw) return refuse(-105, "%s: the argument block is NULL", who);
+  if (!now) return refuse(-105, "%s: now is NULL", who);
+  if (sw->mode != NOAHMP_SW_LINEAR && sw->mode != NOAHMP_SW_ZENITH)
+    return refuse(-105, "%s: mode %d (NOAHMP_SW_LINEAR, NOAHMP_SW_ZENITH)", who, sw->mode);
+  if (bad_count(ncell)) return refuse(-105, "%s: 0 .. 2^31 - 1 columns", who);
+  if (!sw->sw_a || !sw->xlat || !sw->lon || !sw->swdown) return refuse(-105, "%s: sw_a, xlat, lon and swdown are required", who);
   const bool zenith = sw->mode == NOAHMP_SW_ZENITH;
-  if (zenith && !sw->mean_a) return refuse(-105, who, "NOAHMP_SW_ZENITH needs mean_a (noahmp_hip_forcing_cosz_mean)");
+  if (zenith && !sw->mean_a) return refuse(-105, "%s: NOAHMP_SW_ZENITH needs mean_a (noahmp_hip_forcing_cosz_mean)", who);
   const int nnormal = (sw->normal_e ? 1 : 0) + (sw->normal_n ? 1 : 0) + (sw->normal_u ? 1 : 0);
-  if (nnormal != 0 && nnormal != 3) return refuse(-105, who, "normal_e, normal_n and normal_u go together: all three or none");
+  if (nnormal != 0 && nnormal != 3) return refuse(-105, "%s: normal_e, normal_n and normal_u go together: all three or none", who);
   const bool has_b = !zenith && sw->sw_b;
   if (has_b && (sw->idts2 <= 0 || sw->idts < 0 || sw->idts > sw->idts2))
-    return refuse(-105, who, "target date outside the bracketing records (idts, idts2)");
+    return refuse(-105, "%s: target date outside the bracketing records (idts, idts2)", who);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   SwKArgs& k = *out;
@@ -195,23 +178,19 @@ extern "C" {
 int noahmp_hip_forcing_cosz_mean(const float* xlat, const float* lon, int64_t ncell, int nsample, const noahmp_sun_time* times, float* mean,
                                  void* stream) {
   static const char* who = "noahmp_hip_forcing_cosz_mean";
-  if (nsample < 1 || nsample > kMaxSamples) {
-    char b[120];
-    snprintf(b, sizeof b, "1..%d samples per interval (nsample = %d)", kMaxSamples, nsample);
-    return refuse(-107, who, b);
-  }
-  if (!times) return refuse(-105, who, "times is NULL");
-  if (ncell < 0 || ncell > 0x7FFFFFFFL) return refuse(-105, who, "0 .. 2^31 - 1 columns");
-  if (!xlat || !lon || !mean) return refuse(-105, who, "xlat, lon and mean are required");
+  if (nsample < 1 || nsample > kMaxSamples) return refuse(-107, "%s: 1..%d samples per interval (nsample = %d)", who, kMaxSamples, nsample);
+  if (!times) return refuse(-105, "%s: times is NULL", who);
+  if (bad_count(ncell)) return refuse(-105, "%s: 0 .. 2^31 - 1 columns", who);
+  if (!xlat || !lon || !mean) return refuse(-105, "%s: xlat, lon and mean are required", who);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   MeanKArgs k;
   memset(&k, 0, sizeof(k));
   k.xlat = xlat; k.lon = lon; k.mean = mean; k.ncell = ncell; k.nsample = nsample;
   for (int i = 0; i < nsample; i++) k.t[i] = sun_of(times[i]);
-  hipLaunchKernelGGL(noahmp_cosz_mean_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  hipLaunchKernelGGL(noahmp_cosz_mean_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -222,11 +201,11 @@ int noahmp_hip_forcing_shortwave(const noahmp_shortwave* sw, int64_t ncell, cons
   int rc = sw_prepare(who, sw, ncell, now, &k);
   if (rc) return rc;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   const bool zenith = k.p.mode == NOAHMP_SW_ZENITH;
   const bool vec = !zenith && !k.p.has_normal && (ncell & 3) == 0 && aligned16(k.sw_a) && aligned16(k.p.has_b ? k.sw_b : nullptr) && aligned16(k.swdown);
   const long nthread = vec ? ncell / 4 : ncell;
-  const dim3 grid((unsigned)((nthread + kBlock - 1) / kBlock));
+  const dim3 grid = grid_1d(nthread, kBlock);
   if (vec) hipLaunchKernelGGL(noahmp_shortwave_kernel<true>, grid, dim3(kBlock), 0, s, k);
   else hipLaunchKernelGGL(noahmp_shortwave_kernel<false>, grid, dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
@@ -235,32 +214,32 @@ int noahmp_hip_forcing_shortwave(const noahmp_shortwave* sw, int64_t ncell, cons
 
 int noahmp_hip_forcing_shortwave_lit(const noahmp_shortwave* sw, const float* lit, int64_t ncell, const noahmp_sun_time* now, void* stream) {
   static const char* who = "noahmp_hip_forcing_shortwave_lit";
-  if (!lit) return refuse(-105, who, "lit is NULL (noahmp_hip_forcing_shadow makes it)");
+  if (!lit) return refuse(-105, "%s: lit is NULL (noahmp_hip_forcing_shadow makes it)", who);
   SwKArgs k;
   int rc = sw_prepare(who, sw, ncell, now, &k);
   if (rc) return rc;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
-  hipLaunchKernelGGL(noahmp_shortwave_lit_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k, lit);
+  hipStream_t s = stream_of(stream);
+  hipLaunchKernelGGL(noahmp_shortwave_lit_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k, lit);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 int noahmp_hip_forcing_radiation_sky(const noahmp_shortwave* sw, const noahmp_sky* sky, int64_t ncell, const noahmp_sun_time* now, void* stream) {
   static const char* who = "noahmp_hip_forcing_radiation_sky";
-  if (!sky) return refuse(-105, who, "the sky block is NULL");
-  if (!sky->svf) return refuse(-105, who, "svf is NULL (noahmp_hip_skyview makes it)");
-  if (sky->glw && !sky->tsurf) return refuse(-105, who, "glw needs tsurf");
+  if (!sky) return refuse(-105, "%s: the sky block is NULL", who);
+  if (!sky->svf) return refuse(-105, "%s: svf is NULL (noahmp_hip_skyview makes it)", who);
+  if (sky->glw && !sky->tsurf) return refuse(-105, "%s: glw needs tsurf", who);
   SwKArgs k;
   int rc = sw_prepare(who, sw, ncell, now, &k);
   if (rc) return rc;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   SkyKArgs y;
   memset(&y, 0, sizeof(y));
   y.svf = sky->svf; y.lit = sky->lit; y.albedo = sky->albedo; y.glw = sky->glw; y.tsurf = sky->tsurf; y.emiss = sky->emiss;
   y.albedo_const = sky->albedo_const; y.emiss_const = sky->emiss_const; y.sigma = sky->sigma;
-  hipLaunchKernelGGL(noahmp_radiation_sky_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k, y);
+  hipLaunchKernelGGL(noahmp_radiation_sky_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k, y);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -24,7 +24,7 @@
 #include "nmp_engine_host.hpp"
 
 using namespace nmp;
-using nmp_host::g;
+using nmp_host::g, nmp_host::refuse, nmp_host::bad_count, nmp_host::bad_window, nmp_host::bad_spacing, nmp_host::stream_of, nmp_host::grid_1d;
 
 #ifndef NMP_SKYVIEW_INFLIGHT
 #define NMP_SKYVIEW_INFLIGHT 4
@@ -54,44 +54,31 @@ __global__ void __launch_bounds__(kBlock) noahmp_skyview_kernel(const SkyKArgs k
   k.svf[d] = sky_cell<kInFlight>(k.height, k.ni, k.nj, i, j, k.nstep, k.ndir, k.dirs);
 }
 
-int refuse(const char* what) {
-  char b[240];
-  snprintf(b, sizeof b, "noahmp_hip_skyview: %s", what);
-  g.last_error = b;
-  return -105;
-}
-
 }  // namespace
 
 extern "C" {
 
 int noahmp_hip_skyview(const noahmp_skyview* sv, int64_t ndst, void* stream) {
-  if (!sv) return refuse("the argument block is NULL");
-  if (!sv->height || !sv->svf || !sv->dir_x || !sv->dir_y) return refuse("height, svf, dir_x and dir_y are required");
-  if (sv->ni < 0 || sv->nj < 0 || (int64_t)sv->ni * (int64_t)sv->nj > 0x7FFFFFFFL) return refuse("window: ni, nj >= 0 and ni*nj <= 2^31 - 1");
-  if (sv->nstep < 1 || sv->nstep > NOAHMP_SHADOW_MAX_NSTEP) {
-    char b[120];
-    snprintf(b, sizeof b, "nstep %d (1 .. %d cells)", sv->nstep, NOAHMP_SHADOW_MAX_NSTEP);
-    return refuse(b);
-  }
-  if (sv->ndir < 1 || sv->ndir > kMaxDir) {
-    char b[120];
-    snprintf(b, sizeof b, "ndir %d (1 .. %d directions)", sv->ndir, kMaxDir);
-    return refuse(b);
-  }
-  if (!(isfinite(sv->dx) && sv->dx > 0.f && isfinite(sv->dy) && sv->dy > 0.f)) return refuse("dx and dy must be finite and > 0");
-  if (ndst < 0 || ndst > 0x7FFFFFFFL) return refuse("ndst: 0 .. 2^31 - 1");
+  static const char* who = "noahmp_hip_skyview";
+  if (!sv) return refuse(-105, "%s: the argument block is NULL", who);
+  if (!sv->height || !sv->svf || !sv->dir_x || !sv->dir_y) return refuse(-105, "%s: height, svf, dir_x and dir_y are required", who);
+  if (bad_window(sv->ni, sv->nj)) return refuse(-105, "%s: window: ni, nj >= 0 and ni*nj <= 2^31 - 1", who);
+  if (sv->nstep < 1 || sv->nstep > NOAHMP_SHADOW_MAX_NSTEP)
+    return refuse(-105, "%s: nstep %d (1 .. %d cells)", who, sv->nstep, NOAHMP_SHADOW_MAX_NSTEP);
+  if (sv->ndir < 1 || sv->ndir > kMaxDir) return refuse(-105, "%s: ndir %d (1 .. %d directions)", who, sv->ndir, kMaxDir);
+  if (bad_spacing(sv->dx, sv->dy)) return refuse(-105, "%s: dx and dy must be finite and > 0", who);
+  if (bad_count(ndst)) return refuse(-105, "%s: ndst: 0 .. 2^31 - 1", who);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   const long ncell = (long)sv->ni * sv->nj;
   if (ndst == 0 || ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   SkyKArgs k;
   memset(&k, 0, sizeof(k));
   k.height = sv->height; k.dst_index = sv->dst_index; k.svf = sv->svf; k.ncell = ncell; k.ndst = ndst;
   k.ni = sv->ni; k.nj = sv->nj; k.nstep = sv->nstep; k.ndir = sv->ndir;
   for (int q = 0; q < sv->ndir; q++) k.dirs[q] = sky_dir(sv->dir_x[q], sv->dir_y[q], sv->dx, sv->dy);
-  hipLaunchKernelGGL(noahmp_skyview_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  hipLaunchKernelGGL(noahmp_skyview_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -18,7 +18,7 @@
 #include "nmp_engine_host.hpp"
 
 using namespace nmp;
-using nmp_host::g;
+using nmp_host::g, nmp_host::refuse, nmp_host::bad_count, nmp_host::bad_window, nmp_host::bad_spacing, nmp_host::stream_of, nmp_host::grid_1d;
 
 namespace {
 
@@ -62,56 +62,46 @@ __global__ void __launch_bounds__(kBlock) noahmp_forcing_wind_kernel(const WindK
   k.v[c] = v;
 }
 
-int refuse(const char* call, const char* what) {
-  char b[240];
-  snprintf(b, sizeof b, "%s: %s", call, what);
-  g.last_error = b;
-  return -105;
-}
-
 }  // namespace
 
 extern "C" {
 
 int noahmp_hip_wind_terrain(const noahmp_wind_terrain* wt, int64_t ndst, void* stream) {
   const char* me = "noahmp_hip_wind_terrain";
-  if (!wt) return refuse(me, "the argument block is NULL");
-  if (!wt->height || !wt->sx || !wt->sy || !wt->curv) return refuse(me, "height, sx, sy and curv are required");
-  if ((wt->cosalpha != nullptr) != (wt->sinalpha != nullptr)) return refuse(me, "cosalpha and sinalpha go together: both or none");
-  if (wt->ni < 0 || wt->nj < 0 || (int64_t)wt->ni * (int64_t)wt->nj > 0x7FFFFFFFL) return refuse(me, "window: ni, nj >= 0 and ni*nj <= 2^31 - 1");
-  if (wt->ncurv < 1 || wt->ncurv > NOAHMP_WIND_MAX_NCURV) {
-    char b[120];
-    snprintf(b, sizeof b, "ncurv %d (1 .. %d cells)", wt->ncurv, NOAHMP_WIND_MAX_NCURV);
-    return refuse(me, b);
-  }
-  if (!(isfinite(wt->dx) && wt->dx > 0.f && isfinite(wt->dy) && wt->dy > 0.f)) return refuse(me, "dx and dy must be finite and > 0");
-  if (ndst < 0 || ndst > 0x7FFFFFFFL) return refuse(me, "ndst: 0 .. 2^31 - 1");
+  if (!wt) return refuse(-105, "%s: the argument block is NULL", me);
+  if (!wt->height || !wt->sx || !wt->sy || !wt->curv) return refuse(-105, "%s: height, sx, sy and curv are required", me);
+  if ((wt->cosalpha != nullptr) != (wt->sinalpha != nullptr)) return refuse(-105, "%s: cosalpha and sinalpha go together: both or none", me);
+  if (bad_window(wt->ni, wt->nj)) return refuse(-105, "%s: window: ni, nj >= 0 and ni*nj <= 2^31 - 1", me);
+  if (wt->ncurv < 1 || wt->ncurv > NOAHMP_WIND_MAX_NCURV)
+    return refuse(-105, "%s: ncurv %d (1 .. %d cells)", me, wt->ncurv, NOAHMP_WIND_MAX_NCURV);
+  if (bad_spacing(wt->dx, wt->dy)) return refuse(-105, "%s: dx and dy must be finite and > 0", me);
+  if (bad_count(ndst)) return refuse(-105, "%s: ndst: 0 .. 2^31 - 1", me);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   const long ncell = (long)wt->ni * wt->nj;
   if (ndst == 0 || ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   WindTerrainKArgs k;
   memset(&k, 0, sizeof(k));
   k.height = wt->height; k.cosalpha = wt->cosalpha; k.sinalpha = wt->sinalpha; k.dst_index = wt->dst_index;
   k.sx = wt->sx; k.sy = wt->sy; k.curv = wt->curv; k.ncell = ncell; k.ndst = ndst;
   k.p = wind_terrain_params(wt->ni, wt->nj, wt->ncurv, wt->cosalpha ? 1 : 0, wt->dx, wt->dy);
-  hipLaunchKernelGGL(noahmp_wind_terrain_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  hipLaunchKernelGGL(noahmp_wind_terrain_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 int noahmp_hip_forcing_wind(const noahmp_wind* w, int64_t ncell, void* stream) {
   const char* me = "noahmp_hip_forcing_wind";
-  if (!w) return refuse(me, "the argument block is NULL");
-  if (!w->u || !w->v || !w->sx || !w->sy || !w->curv) return refuse(me, "u, v, sx, sy and curv are required");
-  if (!(isfinite(w->slope_max) && w->slope_max > 0.f)) return refuse(me, "slope_max must be finite and > 0");
-  if (!(isfinite(w->curv_max) && w->curv_max > 0.f)) return refuse(me, "curv_max must be finite and > 0");
-  if (ncell < 0 || ncell > 0x7FFFFFFFL) return refuse(me, "ncell: 0 .. 2^31 - 1 columns");
+  if (!w) return refuse(-105, "%s: the argument block is NULL", me);
+  if (!w->u || !w->v || !w->sx || !w->sy || !w->curv) return refuse(-105, "%s: u, v, sx, sy and curv are required", me);
+  if (!(isfinite(w->slope_max) && w->slope_max > 0.f)) return refuse(-105, "%s: slope_max must be finite and > 0", me);
+  if (!(isfinite(w->curv_max) && w->curv_max > 0.f)) return refuse(-105, "%s: curv_max must be finite and > 0", me);
+  if (bad_count(ncell)) return refuse(-105, "%s: ncell: 0 .. 2^31 - 1 columns", me);
   int rc = nmp_host::ensure_init();
   if (rc) return rc;
   if (ncell == 0) return 0;
-  hipStream_t s = stream ? (hipStream_t)stream : g.own_stream;
+  hipStream_t s = stream_of(stream);
   WindKArgs k;
   memset(&k, 0, sizeof(k));
   k.u = w->u; k.v = w->v; k.sx = w->sx; k.sy = w->sy; k.curv = w->curv; k.ncell = ncell;
@@ -119,7 +109,7 @@ int noahmp_hip_forcing_wind(const noahmp_wind* w, int64_t ncell, void* stream) {
   k.p.dc = w->curv_max + w->curv_max;
   k.p.gamma_s = w->gamma_s; k.p.gamma_c = w->gamma_c;
   k.p.turn = (w->flags & NOAHMP_WIND_TURN) ? 1 : 0;
-  hipLaunchKernelGGL(noahmp_forcing_wind_kernel, dim3((unsigned)((ncell + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k);
+  hipLaunchKernelGGL(noahmp_forcing_wind_kernel, grid_1d(ncell, kBlock), dim3(kBlock), 0, s, k);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -19,6 +19,13 @@ class NoahMPFatal(RuntimeError):
         self.code, self.i, self.j = code, i, j
 
 
+def _fill(block, keep):
+    """block.<name> = the address of keep[name] (NULL for None); the tensors live as long as the block."""
+    for name, t in keep.items():
+        setattr(block, name, t.data_ptr() if t is not None else None)
+    block._keep = keep
+
+
 class Engine:
     """Thin handle on libnoahmp_hip.so (one per process == one per GPU/MPI rank)."""
 
@@ -43,6 +50,12 @@ class Engine:
         """True if the library was built with the reference libm's algorithms (bit-identical results)."""
         return self.lib.noahmp_hip_set_option(b"exact_libm", -1) == 1
 
+    def _call(self, name, *args):
+        """lib.<name>(*args); a return code other than 0 raises with the library's text."""
+        rc = getattr(self.lib, name)(*args)
+        if rc:
+            raise RuntimeError("%s: rc=%d %s" % (name, rc, self.lib.noahmp_hip_last_error().decode()))
+
     def set_option(self, key, value):
         return self.lib.noahmp_hip_set_option(key.encode(), int(value))
 
@@ -56,9 +69,7 @@ class Engine:
 
     def fetch(self):
         """Bring the host arrays of a resident run ("resident_state" + "lazy_download") up to date."""
-        rc = self.lib.noahmp_hip_fetch(None)
-        if rc:
-            raise RuntimeError("noahmp_hip_fetch: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_fetch", None)
 
     def noahmplsm(self, store, itimestep, yr, julian, stream=None, check=True):
         a = store.step_args(itimestep, yr, julian)
@@ -103,23 +114,17 @@ class Engine:
 
     def wtable_mmf_async(self, wargs, stream=None):
         """Enqueue one WTABLE_mmf_noahmp call described by a prepared WtableArgs block (store.wtable_args(), device pointers)."""
-        rc = self.lib.noahmp_hip_wtable_mmf_async(C.byref(wargs), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_wtable_mmf_async: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_wtable_mmf_async", C.byref(wargs), stream)
 
     def wtable_lateral_async(self, wargs, qlat, stream=None):
         """First half of WTABLE_mmf_noahmp for a sorted run: KCELL / HEAD + the QLAT stencil on the TILE-order planes of `wargs`
         (wtd, fdepth, topo, isltyp with the ring; xland, xice, ivgtyp, area) -> `qlat` (device tensor shaped like the memory block)."""
-        rc = self.lib.noahmp_hip_wtable_lateral_async(C.byref(wargs), qlat.data_ptr(), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_wtable_lateral_async: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_wtable_lateral_async", C.byref(wargs), qlat.data_ptr(), stream)
 
     def wtable_columns_async(self, wargs, qlat, stream=None):
         """Second half: river flux, deep recharge, UPDATEWTD and the accumulators on a block whose columns are in any order, QLAT
         taken from `qlat` (same order)."""
-        rc = self.lib.noahmp_hip_wtable_columns_async(C.byref(wargs), qlat.data_ptr(), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_wtable_columns_async: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_wtable_columns_async", C.byref(wargs), qlat.data_ptr(), stream)
 
     def forcing_prep(self, store, lon, rain_rate, iday, ihour, iminute=0, isecond=0, scale_vegfra=False, stream=None,
                      first_step=False, wait=True):
@@ -265,10 +270,8 @@ class Engine:
         counts = (C.c_int64 * 3)()
         torch.cuda.current_stream().synchronize()          # tensors written by torch kernels are read on the engine's stream
         self.lib.noahmp_hip_sort_set_band(store.a[band].data_ptr() if band else None)
-        rc = self.lib.noahmp_hip_sort_columns(C.byref(a), flags, int(round(tsk_bin * 1000)) if tsk_bin else 0,
+        self._call("noahmp_hip_sort_columns", C.byref(a), flags, int(round(tsk_bin * 1000)) if tsk_bin else 0,
                                               perm.data_ptr(), keys.data_ptr(), counts, None)
-        if rc:
-            raise RuntimeError("noahmp_hip_sort_columns: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
         # The sorted block's arrays are carved out of ONE allocation, packed back to back (256-byte aligned, each start one odd multiple of
         # 256 B further): separately allocated planes all start on 2 MiB boundaries, so the words of one column sit at the same offset in
         # 2 MiB-aligned regions of all 115 arrays -- the column kernel's wavefront then asks for 206 lines whose low address bits agree.
@@ -318,9 +321,7 @@ class Engine:
         changed = C.c_int64(0)
         band = getattr(store, "sort_band", None)
         self.lib.noahmp_hip_sort_set_band(store.a[band].data_ptr() if band else None)      # the key the store was sorted by
-        rc = self.lib.noahmp_hip_sort_staleness(C.byref(a), store.sort_flags, store.sort_keys.data_ptr(), C.byref(changed), None)
-        if rc:
-            raise RuntimeError("noahmp_hip_sort_staleness: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_sort_staleness", C.byref(a), store.sort_flags, store.sort_keys.data_ptr(), C.byref(changed), None)
         return int(changed.value)
 
     def sort_staleness_async(self, store, stream=None):
@@ -329,9 +330,7 @@ class Engine:
         a = store.step_args(1, 2000, 1.0)
         band = getattr(store, "sort_band", None)
         self.lib.noahmp_hip_sort_set_band(store.a[band].data_ptr() if band else None)
-        rc = self.lib.noahmp_hip_sort_staleness_async(C.byref(a), store.sort_flags, store.sort_keys.data_ptr(), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_sort_staleness_async: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_sort_staleness_async", C.byref(a), store.sort_flags, store.sort_keys.data_ptr(), stream)
 
     def sort_staleness_result(self, wait=True):
         """The count sort_staleness_async asked for; None if it has not arrived and wait is False."""
@@ -434,10 +433,8 @@ class Engine:
         if not isinstance(entries, C.Array):
             entries = Engine.history_entries(entries)
         a = store if isinstance(store, abi.StepArgs) else store.step_args(1, 2000, 1.0)
-        rc = self.lib.noahmp_hip_history_step(entries._n, entries, C.byref(probes) if probes is not None else None, C.byref(a),
+        self._call("noahmp_hip_history_step", entries._n, entries, C.byref(probes) if probes is not None else None, C.byref(a),
                                               count.data_ptr() if count is not None else None, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_history_step: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
     def history_finish(self, entries, dst, flags, count, store, perm=None, fill=None, mask_water=True, stream=None):
         """Output-time finish (noahmp_hip_history_finish): dst[f] (tile-order device tensors, None = reset only) <- the accumulators,
@@ -455,12 +452,10 @@ class Engine:
             return sum(abi.HIST_FIN[x] for x in ((f,) if isinstance(f, str) else f))
         dp = (C.c_void_p * max(n, 1))(*[(t.data_ptr() if t is not None else None) for t in dst])
         fl = (C.c_uint32 * max(n, 1))(*[bits(f) for f in flags])
-        rc = self.lib.noahmp_hip_history_finish(n, entries, dp, fl, count.data_ptr() if count is not None else None,
+        self._call("noahmp_hip_history_finish", n, entries, dp, fl, count.data_ptr() if count is not None else None,
                                                 perm.data_ptr() if perm is not None else None,
                                                 store.a["ivgtyp"].data_ptr() if mask_water else None, store.cfg.iswater,
                                                 float(UNDEFINED if fill is None else fill), store.ni, store.nj, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_history_finish: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
     # ---- region series: per-step weighted sums / minima / maxima over labelled regions (noahmp_regions.hip; helper: history.py::Regions)
     class RegionPlan:
@@ -478,22 +473,16 @@ class Engine:
         nj, ni = region_map.shape
         assert region_map.dtype == torch.int32 and (weight is None or weight.dtype == torch.float32)
         words = C.c_int64(0)
-        rc = self.lib.noahmp_hip_region_plan_size(ni, nj, int(nregion), C.byref(words))
-        if rc:
-            raise RuntimeError("noahmp_hip_region_plan_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_region_plan_size", ni, nj, int(nregion), C.byref(words))
         plan = torch.empty((words.value + 1) // 2, dtype=torch.int64, device=region_map.device).view(torch.int32)
         torch.cuda.current_stream().synchronize()
-        rc = self.lib.noahmp_hip_region_plan(region_map.data_ptr(), weight.data_ptr() if weight is not None else None, ni, nj, int(nregion),
+        self._call("noahmp_hip_region_plan", region_map.data_ptr(), weight.data_ptr() if weight is not None else None, ni, nj, int(nregion),
                                              inv_perm.data_ptr() if inv_perm is not None else None, plan.data_ptr(), plan.numel(), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_region_plan: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
         return Engine.RegionPlan(plan, ni, nj, int(nregion))
 
     def region_follow(self, rp, inv_perm, stream=None):
         """After a re-sort: the members' positions for the new column order (noahmp_hip_region_plan_follow; enqueued only)."""
-        rc = self.lib.noahmp_hip_region_plan_follow(rp.plan.data_ptr(), inv_perm.data_ptr() if inv_perm is not None else None, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_region_plan_follow: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_region_plan_follow", rp.plan.data_ptr(), inv_perm.data_ptr() if inv_perm is not None else None, stream)
         rp.scratch = None
 
     @staticmethod
@@ -512,9 +501,7 @@ class Engine:
 
     def region_scratch_bytes(self, rp, n):
         b = C.c_int64(0)
-        rc = self.lib.noahmp_hip_region_scratch_size(rp.plan.data_ptr(), n, C.byref(b))
-        if rc:
-            raise RuntimeError("noahmp_hip_region_scratch_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_region_scratch_size", rp.plan.data_ptr(), n, C.byref(b))
         return int(b.value)
 
     def region_step(self, rp, entries, store, series, slot, acc=None, stream=None):
@@ -529,10 +516,8 @@ class Engine:
         if rp.scratch is None or rp.scratch.numel() * 8 < need:
             rp.scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=rp.plan.device)
             torch.cuda.current_stream().synchronize()
-        rc = self.lib.noahmp_hip_region_step(rp.plan.data_ptr(), entries._n, entries, C.byref(a), series.data_ptr(), int(series.shape[0]), int(slot),
+        self._call("noahmp_hip_region_step", rp.plan.data_ptr(), entries._n, entries, C.byref(a), series.data_ptr(), int(series.shape[0]), int(slot),
                                              acc.data_ptr() if acc is not None else None, rp.scratch.data_ptr(), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_region_step: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
     # ---- forcing regrid: coarse records -> the model grid's planes (noahmp_regrid.hip; helper: noahmp_amd/regrid.py)
     @staticmethod
@@ -551,17 +536,13 @@ class Engine:
         assert xlat.dtype == torch.float32 and xlon.dtype == torch.float32 and xlat.is_contiguous() and xlon.is_contiguous()
         assert valid is None or (valid.dtype == torch.uint8 and valid.is_contiguous() and valid.numel() == source.nx * source.ny)
         words = C.c_int64(0)
-        rc = self.lib.noahmp_hip_regrid_plan_size(ni, nj, C.byref(words))
-        if rc:
-            raise RuntimeError("noahmp_hip_regrid_plan_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_regrid_plan_size", ni, nj, C.byref(words))
         plan = torch.empty(words.value, dtype=torch.int32, device=xlat.device)
         torch.cuda.current_stream().synchronize()
         unfilled = C.c_int32(0)
-        rc = self.lib.noahmp_hip_regrid_plan_latlon(xlat.data_ptr(), xlon.data_ptr(), ni, nj, C.byref(source),
+        self._call("noahmp_hip_regrid_plan_latlon", xlat.data_ptr(), xlon.data_ptr(), ni, nj, C.byref(source),
                                                     valid.data_ptr() if valid is not None else None, int(search_radius), plan.data_ptr(),
                                                     plan.numel(), C.byref(unfilled), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_regrid_plan_latlon: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
         return plan, int(unfilled.value)
 
     @staticmethod
@@ -584,9 +565,7 @@ class Engine:
         filled or permuted): one kernel launch, enqueued only (noahmp_hip_forcing_regrid)."""
         if not isinstance(entries, C.Array):
             entries = Engine.regrid_entries(entries)
-        rc = self.lib.noahmp_hip_forcing_regrid(plan.data_ptr(), int(ncell), C.byref(source), entries._n, entries, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_forcing_regrid: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_forcing_regrid", plan.data_ptr(), int(ncell), C.byref(source), entries._n, entries, stream)
 
     @staticmethod
     def regrid_met(src_t, src_p, src_q, dst_t, dst_p, dst_q, dz, src_lw=None, dst_lw=None, lapse=-0.0065, fill=float("nan")):
@@ -595,10 +574,8 @@ class Engine:
         returned block."""
         m = abi.RegridMet()
         keep = dict(src_t=src_t, src_p=src_p, src_q=src_q, src_lw=src_lw, dst_t=dst_t, dst_p=dst_p, dst_q=dst_q, dst_lw=dst_lw, dz=dz)
-        for name, t in keep.items():
-            setattr(m, name, t.data_ptr() if t is not None else None)
+        _fill(m, keep)
         m.lapse, m.fill = float(lapse), float(fill)
-        m._keep = keep
         return m
 
     def forcing_regrid_met(self, plan, ncell, source, met, entries, stream=None):
@@ -606,9 +583,7 @@ class Engine:
         plus the 0..32 ordinary entries, in one kernel launch, enqueued only (noahmp_hip_forcing_regrid_met)."""
         if not isinstance(entries, C.Array):
             entries = Engine.regrid_entries(entries)
-        rc = self.lib.noahmp_hip_forcing_regrid_met(plan.data_ptr(), int(ncell), C.byref(source), C.byref(met), entries._n, entries, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_forcing_regrid_met: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_forcing_regrid_met", plan.data_ptr(), int(ncell), C.byref(source), C.byref(met), entries._n, entries, stream)
 
     # ---- budget-preserving regrid of fluxes (noahmp_regrid_conserve.hip; helper: noahmp_amd/regrid.py)
     class RegridConservePlan:
@@ -628,17 +603,13 @@ class Engine:
         assert area is None or (area.dtype == torch.float32 and area.is_contiguous() and area.numel() == ni * nj)
         assert dst_index is None or (dst_index.dtype == torch.int32 and dst_index.is_contiguous() and dst_index.numel() == ni * nj)
         words = C.c_int64(0)
-        rc = self.lib.noahmp_hip_regrid_conserve_plan_size(ni, nj, C.byref(source), C.byref(words))
-        if rc:
-            raise RuntimeError("noahmp_hip_regrid_conserve_plan_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_regrid_conserve_plan_size", ni, nj, C.byref(source), C.byref(words))
         cplan = torch.empty((words.value + 1) // 2, dtype=torch.int64, device=regrid_plan.device).view(torch.int32)
         torch.cuda.current_stream().synchronize()
         clipped = C.c_int32(0)
-        rc = self.lib.noahmp_hip_regrid_conserve_plan(regrid_plan.data_ptr(), ni, nj, C.byref(source), area.data_ptr() if area is not None else None,
+        self._call("noahmp_hip_regrid_conserve_plan", regrid_plan.data_ptr(), ni, nj, C.byref(source), area.data_ptr() if area is not None else None,
                                                       dst_index.data_ptr() if dst_index is not None else None, int(domain_edges),
                                                       cplan.data_ptr(), cplan.numel(), C.byref(clipped), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_regrid_conserve_plan: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
         return Engine.RegridConservePlan(cplan, regrid_plan, ni, nj, source, int(clipped.value))
 
     @staticmethod
@@ -658,9 +629,7 @@ class Engine:
 
     def regrid_conserve_scratch_bytes(self, cp, n):
         b = C.c_int64(0)
-        rc = self.lib.noahmp_hip_regrid_conserve_scratch_size(cp.cplan.data_ptr(), n, C.byref(b))
-        if rc:
-            raise RuntimeError("noahmp_hip_regrid_conserve_scratch_size: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_regrid_conserve_scratch_size", cp.cplan.data_ptr(), n, C.byref(b))
         return int(b.value)
 
     def forcing_regrid_conserve(self, cp, entries, dst_index=None, group_sum=None, stream=None):
@@ -675,12 +644,10 @@ class Engine:
         if cp.scratch is None or cp.scratch.numel() * 8 < need:
             cp.scratch = torch.empty((need + 7) // 8, dtype=torch.float64, device=cp.cplan.device)
             torch.cuda.current_stream().synchronize()
-        rc = self.lib.noahmp_hip_forcing_regrid_conserve(cp.cplan.data_ptr(), cp.regrid_plan.data_ptr(), C.byref(cp.source),
+        self._call("noahmp_hip_forcing_regrid_conserve", cp.cplan.data_ptr(), cp.regrid_plan.data_ptr(), C.byref(cp.source),
                                                          dst_index.data_ptr() if dst_index is not None else None, int(entries._ndst),
                                                          entries._n, entries, group_sum.data_ptr() if group_sum is not None else None,
                                                          cp.scratch.data_ptr(), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_forcing_regrid_conserve: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
 
     # ---- shortwave forcing: zenith weighting in time, slope and aspect (noahmp_shortwave.hip; helper: noahmp_amd/shortwave.py)
     @staticmethod
@@ -698,9 +665,7 @@ class Engine:
         interval) for every column of the float32 device planes xlat / lon: one kernel launch, enqueued only (noahmp_hip_forcing_cosz_mean)."""
         if not isinstance(times, C.Array):
             times = Engine.sun_times(times)
-        rc = self.lib.noahmp_hip_forcing_cosz_mean(xlat.data_ptr(), lon.data_ptr(), xlat.numel(), times._n, times, mean.data_ptr(), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_forcing_cosz_mean: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_forcing_cosz_mean", xlat.data_ptr(), lon.data_ptr(), xlat.numel(), times._n, times, mean.data_ptr(), stream)
         return mean
 
     @staticmethod
@@ -710,21 +675,17 @@ class Engine:
         b = abi.Shortwave()
         ne, nn, nu = normal if normal is not None else (None, None, None)
         keep = dict(sw_a=sw_a, sw_b=sw_b, mean_a=mean_a, xlat=xlat, lon=lon, normal_e=ne, normal_n=nn, normal_u=nu, swdown=swdown)
-        for name, t in keep.items():
-            setattr(b, name, t.data_ptr() if t is not None else None)
+        _fill(b, keep)
         b.idts, b.idts2 = int(idts), int(idts2)
         b.mode = abi.SW_MODE[mode] if isinstance(mode, str) else int(mode)
         b.max_ratio, b.mu_min, b.max_terrain_ratio, b.solar_constant = float(max_ratio), float(mu_min), float(max_terrain_ratio), float(solar_constant)
-        b._keep = keep
         return b
 
     def forcing_shortwave(self, block, ncell, now, stream=None):
         """Downward shortwave of one step from a block of Engine.shortwave_block at now = (iday, ihour, iminute, isecond): one kernel
         launch, enqueued only (noahmp_hip_forcing_shortwave).  Call it after forcing_interpolate[_prep], whose linear SWDOWN it overwrites."""
         t = Engine.sun_times([now])
-        rc = self.lib.noahmp_hip_forcing_shortwave(C.byref(block), int(ncell), t, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_forcing_shortwave: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_forcing_shortwave", C.byref(block), int(ncell), t, stream)
 
     # ---- cast shadows: terrain ray march and the lit shortwave step (noahmp_shadow.hip, noahmp_shortwave.hip; helper: noahmp_amd/shortwave.py)
     @staticmethod
@@ -736,30 +697,24 @@ class Engine:
         assert height.dim() == 2 and height.is_contiguous() and xlat.numel() == height.numel() and lon.numel() == height.numel()
         b = abi.Shadow()
         keep = dict(height=height, xlat=xlat, lon=lon, cosalpha=cosalpha, sinalpha=sinalpha, dst_index=dst_index, lit=lit)
-        for name, t in keep.items():
-            setattr(b, name, t.data_ptr() if t is not None else None)
+        _fill(b, keep)
         b.nj, b.ni = (int(v) for v in height.shape)
         b.nstep = int(nstep)
         b.dx, b.dy, b.mu_min = float(dx), float(dy), float(mu_min)
         b.height_max = float(height_max) if height_max is not None else (float(height.max().item()) if height.numel() else 0.0)
-        b._keep = keep
         return b
 
     def forcing_shadow(self, block, ndst, now, stream=None):
         """The lit plane of a block of Engine.shadow_block at now = (iday, ihour, iminute, isecond): 1.0 where the cell sees the sun, 0.0
         in a cast shadow.  One kernel launch, enqueued only (noahmp_hip_forcing_shadow)."""
         t = Engine.sun_times([now])
-        rc = self.lib.noahmp_hip_forcing_shadow(C.byref(block), int(ndst), t, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_forcing_shadow: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_forcing_shadow", C.byref(block), int(ndst), t, stream)
 
     def forcing_shortwave_lit(self, block, lit, ncell, now, stream=None):
         """forcing_shortwave with the lit plane (ncell floats, the column order of the block's planes) on the direct beam: one kernel
         launch, enqueued only (noahmp_hip_forcing_shortwave_lit)."""
         t = Engine.sun_times([now])
-        rc = self.lib.noahmp_hip_forcing_shortwave_lit(C.byref(block), lit.data_ptr() if lit is not None else None, int(ncell), t, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_forcing_shortwave_lit: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_forcing_shortwave_lit", C.byref(block), lit.data_ptr() if lit is not None else None, int(ncell), t, stream)
 
     # ---- sky-view factor: horizon scan and the radiation step with it (noahmp_skyview.hip, noahmp_shortwave.hip; helper: noahmp_amd/shortwave.py)
     @staticmethod
@@ -782,8 +737,7 @@ class Engine:
         assert dir_x.size == dir_y.size
         b = abi.Skyview()
         keep = dict(height=height, dst_index=dst_index, svf=svf)
-        for name, t in keep.items():
-            setattr(b, name, t.data_ptr() if t is not None else None)
+        _fill(b, keep)
         b.dir_x, b.dir_y = dir_x.ctypes.data, dir_y.ctypes.data
         b.nj, b.ni = (int(v) for v in height.shape)
         b.nstep, b.ndir = int(nstep), int(dir_x.size)
@@ -794,9 +748,7 @@ class Engine:
     def skyview(self, block, ndst, stream=None):
         """The sky-view factor of a block of Engine.skyview_block: 1.0 where a horizontal receiver sees the whole hemisphere.  One kernel
         launch, enqueued only, once per terrain (noahmp_hip_skyview)."""
-        rc = self.lib.noahmp_hip_skyview(C.byref(block), int(ndst), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_skyview: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_skyview", C.byref(block), int(ndst), stream)
 
     @staticmethod
     def sky_block(svf, lit=None, albedo=0.2, glw=None, tsurf=None, emiss=0.95, sigma=5.67e-8):
@@ -810,19 +762,15 @@ class Engine:
                 planes[name] = v
             else:
                 setattr(b, name + "_const", float(v))
-        for name, t in planes.items():
-            setattr(b, name, t.data_ptr() if t is not None else None)
+        _fill(b, planes)
         b.sigma = float(sigma)
-        b._keep = planes
         return b
 
     def forcing_radiation_sky(self, block, sky, ncell, now, stream=None):
         """forcing_shortwave_lit plus the sky-view terms of the shortwave and the longwave of the closed part of the hemisphere, from a block
         of Engine.shortwave_block and one of Engine.sky_block: one kernel launch, enqueued only (noahmp_hip_forcing_radiation_sky)."""
         t = Engine.sun_times([now])
-        rc = self.lib.noahmp_hip_forcing_radiation_sky(C.byref(block), C.byref(sky), int(ncell), t, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_forcing_radiation_sky: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_forcing_radiation_sky", C.byref(block), C.byref(sky), int(ncell), t, stream)
 
     # ---- terrain-adjusted wind: slope and curvature of the terrain, and the wind of a record (noahmp_wind.hip; helper: noahmp_amd/wind.py)
     @staticmethod
@@ -833,20 +781,16 @@ class Engine:
         assert height.dim() == 2 and height.is_contiguous()
         b = abi.WindTerrain()
         keep = dict(height=height, cosalpha=cosalpha, sinalpha=sinalpha, dst_index=dst_index, sx=sx, sy=sy, curv=curv)
-        for name, t in keep.items():
-            setattr(b, name, t.data_ptr() if t is not None else None)
+        _fill(b, keep)
         b.nj, b.ni = (int(v) for v in height.shape)
         b.ncurv = int(ncurv)
         b.dx, b.dy = float(dx), float(dy)
-        b._keep = keep
         return b
 
     def wind_terrain(self, block, ndst, stream=None):
         """The slope vector (length = the slope angle, pointing uphill) and the curvature of a block of Engine.wind_terrain_block.  One
         kernel launch, enqueued only, once per terrain (noahmp_hip_wind_terrain)."""
-        rc = self.lib.noahmp_hip_wind_terrain(C.byref(block), int(ndst), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_wind_terrain: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_wind_terrain", C.byref(block), int(ndst), stream)
 
     @staticmethod
     def wind_block(u, v, sx, sy, curv, slope_max, curv_max, gamma_s=0.58, gamma_c=0.42, turn=True):
@@ -854,19 +798,15 @@ class Engine:
         slope_max / curv_max the maxima of the whole run, the same numbers on every rank.  The tensors are kept alive by the block."""
         b = abi.Wind()
         keep = dict(u=u, v=v, sx=sx, sy=sy, curv=curv)
-        for name, t in keep.items():
-            setattr(b, name, t.data_ptr() if t is not None else None)
+        _fill(b, keep)
         b.slope_max, b.curv_max, b.gamma_s, b.gamma_c = float(slope_max), float(curv_max), float(gamma_s), float(gamma_c)
         b.flags = abi.WIND_FLAG["turn"] if turn else 0
-        b._keep = keep
         return b
 
     def forcing_wind(self, block, ncell, stream=None):
         """The wind of ncell columns weighted by slope and curvature and (with the TURN flag) turned around the obstacle, in place, from a
         block of Engine.wind_block: one kernel launch, enqueued only (noahmp_hip_forcing_wind)."""
-        rc = self.lib.noahmp_hip_forcing_wind(C.byref(block), int(ncell), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_forcing_wind: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_forcing_wind", C.byref(block), int(ncell), stream)
 
     # ---- runoff routing on a D8 network: directions, upstream bytes, upstream counts, linear reservoirs (noahmp_routing.hip; helper:
     # noahmp_amd/routing.py)
@@ -887,9 +827,7 @@ class Engine:
     def flow_terrain(self, block, stream=None):
         """The direction of steepest strict descent (0 or k = 1..8) of every cell of a block of Engine.flow_terrain_block.  One kernel
         launch, enqueued only, once per terrain (noahmp_hip_flow_terrain)."""
-        rc = self.lib.noahmp_hip_flow_terrain(C.byref(block), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_flow_terrain: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_flow_terrain", C.byref(block), stream)
 
     def flow_inmask(self, dir, inmask, stream=None):
         """The byte of upstream neighbours of every cell of the (nj, ni) uint8 device plane dir, into the uint8 plane inmask.  One kernel
@@ -898,9 +836,7 @@ class Engine:
         assert dir.dim() == 2 and dir.dtype == torch.uint8 and inmask.dtype == torch.uint8 and dir.is_contiguous() and inmask.is_contiguous()
         assert inmask.numel() == dir.numel()
         nj, ni = (int(v) for v in dir.shape)
-        rc = self.lib.noahmp_hip_flow_inmask(dir.data_ptr(), inmask.data_ptr(), ni, nj, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_flow_inmask: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_flow_inmask", dir.data_ptr(), inmask.data_ptr(), ni, nj, stream)
 
     def flow_accumulate(self, inmask, acc_old, acc_new, changed, stream=None):
         """One Jacobi pass of the upstream cell count over the (nj, ni) uint8 device plane inmask: acc_old -> acc_new (int32 tensors holding
@@ -911,9 +847,7 @@ class Engine:
         assert all(t.dtype == torch.int32 and t.is_contiguous() and t.numel() == inmask.numel() for t in (acc_old, acc_new))
         assert changed.dtype == torch.int32 and changed.numel() >= 1
         nj, ni = (int(v) for v in inmask.shape)
-        rc = self.lib.noahmp_hip_flow_accumulate(inmask.data_ptr(), acc_old.data_ptr(), acc_new.data_ptr(), changed.data_ptr(), ni, nj, stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_flow_accumulate: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_flow_accumulate", inmask.data_ptr(), acc_old.data_ptr(), acc_new.data_ptr(), changed.data_ptr(), ni, nj, stream)
 
     @staticmethod
     def route_block(inmask, col_index, area, release, storage, out_old, out_new, runoff_a, runoff_b, scale):
@@ -928,18 +862,15 @@ class Engine:
             if t is not None:
                 assert t.is_contiguous() and (name.startswith("runoff") or t.numel() == inmask.numel()), name
                 assert name in ("inmask", "col_index") or t.dtype == torch.float32, name
-            setattr(b, name, t.data_ptr() if t is not None else None)
+        _fill(b, keep)
         b.nj, b.ni = (int(v) for v in inmask.shape)
         b.scale = float(scale)
-        b._keep = keep
         return b
 
     def route_runoff(self, block, ncol, stream=None):
         """One routing step of a block of Engine.route_block: every owned cell gathers what its upstream neighbours released in the call
         before, adds its column's runoff and releases its fraction.  One kernel launch, enqueued only (noahmp_hip_route_runoff)."""
-        rc = self.lib.noahmp_hip_route_runoff(C.byref(block), int(ncol), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_route_runoff: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_route_runoff", C.byref(block), int(ncol), stream)
 
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
@@ -959,9 +890,7 @@ class Engine:
     def noahmplsm_async(self, args, stream=None):
         """Enqueue one step described by a prepared StepArgs block (store.step_args(...), device pointers)."""
         self._apply_ranges(getattr(args, "_ranges", None))
-        rc = self.lib.noahmp_hip_step_async(C.byref(args), stream)
-        if rc:
-            raise RuntimeError("noahmp_hip_step_async: rc=%d %s" % (rc, self.lib.noahmp_hip_last_error().decode()))
+        self._call("noahmp_hip_step_async", C.byref(args), stream)
 
     def sync(self, check=True):
         """Wait for the pending asynchronous steps; returns (Status, ordinal of the failing step or -1)."""

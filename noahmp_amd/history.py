@@ -22,6 +22,7 @@ import numpy as np
 
 from . import abi
 from .restart import UNDEFINED
+from .tile import inverse_perm, permute_planes, sorted_perm
 
 HUGE = float(np.finfo(np.float32).max)
 _IDENTITY = {"sum": 0.0, "sum_dt": 0.0, "min": HUGE, "max": -HUGE, "last": 0.0}
@@ -85,10 +86,7 @@ class History:
         self._entries = None
 
     def _inverse(self, perm):
-        torch = self.torch
-        inv = torch.empty_like(perm)
-        inv[perm.long()] = torch.arange(perm.numel(), dtype=perm.dtype, device=perm.device)
-        return inv
+        return inverse_perm(perm)
 
     def _probe_columns(self):
         if self.probe_points is None:
@@ -124,20 +122,11 @@ class History:
     def follow(self, store=None):
         """After Engine.sort_store(store): bring the accumulators, the count and the probe columns into the store's new column order
         (noahmp_hip_gather_fields).  Waits for the engine's stream."""
-        torch = self.torch
         if store is not None:
             self.store = store
-        new = getattr(self.store, "sort_perm", None)
-        assert new is not None, "follow() is for a store that Engine.sort_store has sorted"
+        new = sorted_perm(self.store, self.store.ni, self.store.nj)
         g = new if self.perm is None else self._inverse(self.perm)[new.long()].contiguous()   # new position p <- old position g[p]
-        torch.cuda.current_stream().synchronize()
-        old = [it[4] for it in self.items] + [self.count]
-        fresh = [torch.empty_like(t) for t in old]
-        torch.cuda.current_stream().synchronize()
-        self.engine.stream_sync()
-        for i in range(0, len(old), 32):
-            self.engine.gather(fresh[i:i + 32], old[i:i + 32], g, self.store.ni, self.store.nj)()
-        self.engine.stream_sync()
+        fresh = permute_planes(self.engine, [it[4] for it in self.items] + [self.count], g, self.store.ni, self.store.nj)
         for it, t in zip(self.items, fresh):
             it[4] = t
         self.count = fresh[-1]
@@ -214,12 +203,11 @@ class Regions:
         self.plan = engine.region_plan(self.region_map, self.nregion, self.weight, self._inverse(getattr(store, "sort_perm", None)))
 
     def _inverse(self, perm):
+        """inverse_perm(perm), complete before the engine's stream reads it; None for None."""
         if perm is None:
             return None
-        torch = self.torch
-        inv = torch.empty_like(perm)
-        inv[perm.long()] = torch.arange(perm.numel(), dtype=perm.dtype, device=perm.device)
-        torch.cuda.current_stream().synchronize()
+        inv = inverse_perm(perm)
+        self.torch.cuda.current_stream().synchronize()
         return inv
 
     def add(self, name, field, op="sum", level=None):
@@ -263,8 +251,7 @@ class Regions:
         """After Engine.sort_store(store): the members' positions in the store's new column order."""
         if store is not None:
             self.store = store
-        perm = getattr(self.store, "sort_perm", None)
-        assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
+        perm = sorted_perm(self.store, self.store.ni, self.store.nj)
         self.engine.region_follow(self.plan, self._inverse(perm))
         self.engine.stream_sync()
         self._entries = None

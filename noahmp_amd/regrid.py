@@ -18,6 +18,9 @@ against the one global source.
 """
 
 
+from .tile import inverse_perm, permute_planes, sorted_perm, to_tile_order, window_index
+
+
 class ForcingRegrid:
     def __init__(self, engine, xlat, xlon, source, valid=None, search_radius=4, fill=float("nan")):
         import torch
@@ -37,6 +40,7 @@ class ForcingRegrid:
         self.valid, self.search_radius = valid, search_radius
         self.conserve = None                     # set_conserve: the Engine.RegridConservePlan of the window
         self.clipped = 0                         # groups the window cuts (set_conserve); > 0: widen the margin
+        self.window = None                       # set_conserve: ((nj_w, ni_w), (i0, j0)) of the window
         self.window_tile = self.dst_index = None # per window cell: its tile index or -1 / its position in the current column order or -1
         self.patterns = {}                       # name -> plane in window order
 
@@ -69,16 +73,7 @@ class ForcingRegrid:
 
     def _tile_order(self, plane):
         """A tile-order copy of a plane in the current column order: follow() always starts from tile order."""
-        torch = self.torch
-        if self.perm is None:
-            return plane
-        inv = torch.empty_like(self.perm)
-        inv[self.perm.long()] = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
-        tile = torch.empty_like(plane)
-        torch.cuda.current_stream().synchronize()
-        self.engine.gather([tile], [plane], inv, self.ni, self.nj)()
-        self.engine.stream_sync()
-        return tile
+        return to_tile_order(self.engine, plane, self.perm, self.ni, self.nj)
 
     MET_NAMES = ("t", "p", "q", "lw")
 
@@ -112,9 +107,8 @@ class ForcingRegrid:
             nj_w, ni_w = xlat_w.shape
             assert 0 <= i0 and i0 + self.ni <= ni_w and 0 <= j0 and j0 + self.nj <= nj_w, "the window must hold the tile"
             plan_w, _ = self.engine.regrid_plan(xlat_w.contiguous(), xlon_w.contiguous(), self.source, valid=self.valid, search_radius=self.search_radius)
-        tile = torch.full((nj_w, ni_w), -1, dtype=torch.int32, device=self.device)
-        tile[j0:j0 + self.nj, i0:i0 + self.ni] = torch.arange(self.ncell, dtype=torch.int32, device=self.device).reshape(self.nj, self.ni)
-        self.window_tile = tile.contiguous()
+        self.window = ((nj_w, ni_w), (i0, j0))
+        self.window_tile = window_index(*self.window, self.ni, self.nj, device=self.device)
         if area is not None:
             area = area.to(torch.float32).contiguous()
             assert area.numel() == nj_w * ni_w, "area has the window's shape"
@@ -126,14 +120,10 @@ class ForcingRegrid:
 
     def _refresh_dst_index(self):
         """dst_index of the window cells for the current column order: only this changes after a re-sort."""
-        torch = self.torch
         if self.perm is None:
             self.dst_index = self.window_tile
-            return
-        inv = torch.empty_like(self.perm)
-        inv[self.perm.long()] = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
-        t = self.window_tile
-        self.dst_index = torch.where(t >= 0, inv[t.clamp(min=0).long()], t).to(torch.int32).contiguous()
+        else:
+            self.dst_index = window_index(*self.window, self.ni, self.nj, pos=inverse_perm(self.perm), device=self.device)
 
     def set_pattern(self, name, plane):
         """Conserve plane `name` is shaped by `plane` before it is rescaled (a fine climatology, PRISM-style): a float32 device plane of
@@ -206,24 +196,18 @@ class ForcingRegrid:
         noahmp_hip_gather_fields; the conserve plan keeps its window order and only dst_index is made anew.  Waits for the engine's stream.
         Records made before the call keep the old order."""
         torch = self.torch
-        perm = getattr(store, "sort_perm", None)
-        assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
-        assert store.ni == self.ni and store.nj == self.nj
+        perm = sorted_perm(store, self.ni, self.nj)
         n = self.ncell
         new = torch.empty_like(self.plan_tile)
         names = list(self.adjust_tile)
         fresh = [torch.empty_like(self.adjust_tile[k][0]) for k in names]
         new_dz = torch.empty_like(self.dz_tile) if self.dz_tile is not None else None
-        torch.cuda.current_stream().synchronize()
-        self.engine.stream_sync()
         dst = [new[k * n:(k + 1) * n] for k in range(6)] + fresh
         src = [self.plan_tile[k * n:(k + 1) * n] for k in range(6)] + [self.adjust_tile[k][0] for k in names]
         if new_dz is not None:
             dst.append(new_dz)
             src.append(self.dz_tile)
-        for i in range(0, len(dst), 32):
-            self.engine.gather(dst[i:i + 32], src[i:i + 32], perm, self.ni, self.nj)()
-        self.engine.stream_sync()
+        permute_planes(self.engine, src, perm, self.ni, self.nj, out=dst)
         self.plan, self.perm = new, perm
         self.adjust = {k: (t, self.adjust_tile[k][1]) for k, t in zip(names, fresh)}
         self.dz = new_dz

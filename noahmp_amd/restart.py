@@ -22,6 +22,7 @@ import numpy as np
 
 from . import abi
 from .abi_spec import NSNOW
+from .tile import inverse_perm
 
 MISSING = np.float32(-1.0e33)            # netcdf_io:2189 global attribute and the mask value
 UNDEFINED = np.float32(-1.0e20)          # undefined_real, driver/module_hrldas_noahmp_vars.F90:6
@@ -104,8 +105,7 @@ def fetch(engine, store, names, perm=None, mask=()):
     out = {}
     inv = None
     if perm is not None:
-        inv = torch.empty_like(perm)
-        inv[perm.long()] = torch.arange(perm.numel(), dtype=perm.dtype, device=perm.device)
+        inv = inverse_perm(perm)
         torch.cuda.current_stream().synchronize()      # `inv` is written on torch's stream and read on the engine's own stream
     veg = store.a["ivgtyp"]
     for i in range(0, len(names), 32):

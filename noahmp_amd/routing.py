@@ -20,6 +20,8 @@ import math
 
 import numpy as np
 
+from .tile import check_window, inverse_perm, sorted_perm, window_index
+
 ESRI_CODES = {1: 1, 128: 2, 64: 3, 32: 4, 16: 5, 8: 6, 4: 7, 2: 8}      # ESRI / WRF-Hydro FLOWDIRECTION (E = 1, clockwise) -> k, with j towards north
 NOT_OWNED = -2                                                           # col_index of a ring cell
 
@@ -61,9 +63,8 @@ class FlowNetwork:
         return torch.where((c >= 0) & (c < 256), t[c.clamp(0, 255)], torch.zeros((), dtype=torch.uint8, device=codes.device))
 
     def _block_of(self, shape, origin):
-        i0, j0 = (int(v) for v in origin)
+        i0, j0 = check_window(shape, origin, self.ni, self.nj)
         nj_w, ni_w = shape
-        assert 0 <= i0 and i0 + self.ni <= ni_w and 0 <= j0 and j0 + self.nj <= nj_w, "the window must contain the tile at origin"
         w, s = min(1, i0), min(1, j0)
         e, n = min(1, ni_w - i0 - self.ni), min(1, nj_w - j0 - self.nj)
         return (slice(j0 - s, j0 + self.nj + n), slice(i0 - w, i0 + self.ni + e)), (w, s)
@@ -117,16 +118,13 @@ class FlowNetwork:
     def _index(self):
         torch = self.torch
         dev = self.dir.device
-        pos = torch.arange(self.ncell, dtype=torch.int32, device=dev)
         if self.perm is not None:                                        # sorted position p holds tile column perm[p]
-            inv = torch.empty_like(pos)
-            inv[self.perm.long()] = pos
-            pos = inv
+            pos = inverse_perm(self.perm)
+        else:
+            pos = torch.arange(self.ncell, dtype=torch.int32, device=dev)
         if self.has_input is not None:
             pos = torch.where(self.has_input.reshape(-1), pos, torch.full_like(pos, -1))
-        idx = torch.full(self.dir.shape, NOT_OWNED, dtype=torch.int32, device=dev)
-        self.tile_view(idx).copy_(pos.reshape(self.nj, self.ni))
-        self.col_index = idx.contiguous()
+        self.col_index = window_index(self.dir.shape, (self.i0, self.j0), self.ni, self.nj, pos=pos, fill=NOT_OWNED, device=dev)
         torch.cuda.current_stream().synchronize()
 
     def set_input_columns(self, has_input):
@@ -139,10 +137,7 @@ class FlowNetwork:
 
     def follow(self, store):
         """After Engine.sort_store(store): only col_index is rewritten, from the inverse permutation.  The window planes never move."""
-        perm = getattr(store, "sort_perm", None)
-        assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
-        assert store.ni == self.ni and store.nj == self.nj
-        self.perm = perm
+        self.perm = sorted_perm(store, self.ni, self.nj)
         if self.dir is not None:
             self._index()
 
@@ -241,13 +236,10 @@ class FlowNetwork:
 
     def _auto_input(self, store):
         """Columns with XLAND >= 1.5 (water) or XICE >= XICE_THRES (sea ice) are skipped by the step (drv:426-441): no local input."""
-        torch = self.torch
         xland, xice = store.a["xland"].reshape(-1), store.a["xice"].reshape(-1)
         has = ((xland - 1.5) < 0) & ~(xice >= float(store.cfg.xice_thres))
         if self.perm is not None:                                        # the store is sorted: back to tile order
-            tile = torch.empty_like(has)
-            tile[self.perm.long()] = has
-            has = tile
+            has = has[inverse_perm(self.perm).long()]
         self.set_input_columns(has.reshape(self.nj, self.ni))
 
     def discharge(self):

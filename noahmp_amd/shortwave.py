@@ -17,6 +17,8 @@ every rounding -- is the text in include/noahmp_hip.h.
 """
 import math
 
+from .tile import check_window, inverse_perm, permute_planes, sorted_perm, to_tile_order, window_index
+
 
 def days_in_year(year):
     return 366 if (year % 4 == 0 and (year % 100 != 0 or year % 400 == 0)) else 365
@@ -137,9 +139,7 @@ class Shortwave:
         terrain normals are optional.  Works before or after follow()."""
         torch = self.torch
         assert height.dim() == 2 and (cosalpha is None) == (sinalpha is None) and int(every) >= 1
-        i0, j0 = (int(v) for v in origin)
-        nj_w, ni_w = height.shape
-        assert 0 <= i0 and i0 + self.ni <= ni_w and 0 <= j0 and j0 + self.nj <= nj_w, "the window must contain the tile at origin"
+        i0, j0 = check_window(height.shape, origin, self.ni, self.nj)
         h = height.to(torch.float32).contiguous()
         lat, lon = torch.zeros_like(h), torch.zeros_like(h)      # only tile cells are marched, so only they need a sun
         lat[j0:j0 + self.nj, i0:i0 + self.ni] = self.lat_tile
@@ -159,16 +159,9 @@ class Shortwave:
         """dst_index of the shadow window: the position of every tile cell in the current column order, -1 in the margin."""
         torch = self.torch
         sh = self.shadow
-        i0, j0 = sh["origin"]
-        if self.perm is None:
-            pos = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
-        else:
-            pos = torch.empty(self.ncell, dtype=torch.int32, device=self.device)
-            pos[self.perm.long()] = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
-        index = torch.full(sh["height"].shape, -1, dtype=torch.int32, device=self.device)
-        index[j0:j0 + self.nj, i0:i0 + self.ni] = pos.reshape(self.nj, self.ni)
+        pos = inverse_perm(self.perm) if self.perm is not None else None
         rot = sh["rot"] or (None, None)
-        sh["index"] = index.contiguous()
+        sh["index"] = window_index(sh["height"].shape, sh["origin"], self.ni, self.nj, pos=pos, device=self.device)
         sh["block"] = self.engine.shadow_block(sh["height"], sh["lat"], sh["lon"], self.lit, sh["dx"], sh["dy"], nstep=sh["nstep"], cosalpha=rot[0],
                                                sinalpha=rot[1], dst_index=sh["index"], mu_min=self.par["mu_min"], height_max=sh["height_max"])
         self.shadow_calls = 0
@@ -189,13 +182,8 @@ class Shortwave:
         store.  Works before or after follow()."""
         torch = self.torch
         assert height.dim() == 2
-        i0, j0 = (int(v) for v in origin)
-        nj_w, ni_w = height.shape
-        assert 0 <= i0 and i0 + self.ni <= ni_w and 0 <= j0 and j0 + self.nj <= nj_w, "the window must contain the tile at origin"
+        index = window_index(height.shape, origin, self.ni, self.nj, device=self.device)
         h = height.to(torch.float32).contiguous()
-        index = torch.full(h.shape, -1, dtype=torch.int32, device=self.device)
-        index[j0:j0 + self.nj, i0:i0 + self.ni] = torch.arange(self.ncell, dtype=torch.int32, device=self.device).reshape(self.nj, self.ni)
-        index = index.contiguous()
         self.svf_tile = torch.empty((self.nj, self.ni), dtype=torch.float32, device=self.device)
         torch.cuda.current_stream().synchronize()
         self.engine.skyview(self.engine.skyview_block(h, self.svf_tile, dx, dy, nstep=nstep, ndir=ndir, dst_index=index), self.ncell)
@@ -203,10 +191,7 @@ class Shortwave:
         self.sky = dict(albedo=albedo, emiss=emiss, tsurf=tsurf, longwave=bool(longwave), sigma=float(sigma))
         self.svf = self.svf_tile
         if self.perm is not None:
-            self.svf = torch.empty_like(self.svf_tile)
-            torch.cuda.current_stream().synchronize()
-            self.engine.gather([self.svf], [self.svf_tile], self.perm, self.ni, self.nj)()
-            self.engine.stream_sync()
+            self.svf = permute_planes(self.engine, [self.svf_tile], self.perm, self.ni, self.nj)[0]
 
     def _sky_block(self, store):
         sky = self.sky
@@ -219,30 +204,14 @@ class Shortwave:
                                      emiss=emiss, sigma=sky["sigma"])
 
     def _tile_order(self, plane):
-        torch = self.torch
-        if self.perm is None:
-            return plane
-        inv = torch.empty_like(self.perm)
-        inv[self.perm.long()] = torch.arange(self.ncell, dtype=torch.int32, device=self.device)
-        tile = torch.empty_like(plane)
-        torch.cuda.current_stream().synchronize()
-        self.engine.gather([tile], [plane], inv, self.ni, self.nj)()
-        self.engine.stream_sync()
-        return tile
+        return to_tile_order(self.engine, plane, self.perm, self.ni, self.nj)
 
     def follow(self, store):
         """After Engine.sort_store(store): lat, lon and the normals, permuted into the store's column order with noahmp_hip_gather_fields.
         Waits for the engine's stream.  Interval means made before the call keep the old order: make them again."""
-        torch = self.torch
-        perm = getattr(store, "sort_perm", None)
-        assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
-        assert store.ni == self.ni and store.nj == self.nj
+        perm = sorted_perm(store, self.ni, self.nj)
         src = [self.lat_tile, self.lon_tile] + list(self.normal_tile or ()) + ([self.svf_tile] if self.svf_tile is not None else [])
-        dst = [torch.empty_like(t) for t in src]
-        torch.cuda.current_stream().synchronize()
-        self.engine.stream_sync()
-        self.engine.gather(dst, src, perm, self.ni, self.nj)()
-        self.engine.stream_sync()
+        dst = permute_planes(self.engine, src, perm, self.ni, self.nj)
         self.lat, self.lon, self.perm = dst[0], dst[1], perm
         self.normal = tuple(dst[2:5]) if self.normal_tile is not None else None
         if self.svf_tile is not None:

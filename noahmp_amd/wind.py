@@ -14,6 +14,8 @@ include/noahmp_hip.h.
 """
 import math
 
+from .tile import permute_planes, sorted_perm, window_index
+
 
 class WindTerrain:
     def __init__(self, engine, ni, nj, gamma_s=0.58, gamma_c=0.42):
@@ -38,18 +40,13 @@ class WindTerrain:
         same slope differently.  Works before or after follow()."""
         torch = self.torch
         assert height.dim() == 2 and (cosalpha is None) == (sinalpha is None)
-        i0, j0 = (int(v) for v in origin)
-        nj_w, ni_w = height.shape
-        assert 0 <= i0 and i0 + self.ni <= ni_w and 0 <= j0 and j0 + self.nj <= nj_w, "the window must contain the tile at origin"
         dev = height.device
+        index = window_index(height.shape, origin, self.ni, self.nj, device=dev)
         h = height.to(torch.float32).contiguous()
         rot = (None, None)
         if cosalpha is not None:
             rot = tuple(t.to(torch.float32).contiguous() for t in (cosalpha, sinalpha))
             assert all(t.shape == h.shape for t in rot)
-        index = torch.full(h.shape, -1, dtype=torch.int32, device=dev)
-        index[j0:j0 + self.nj, i0:i0 + self.ni] = torch.arange(self.ncell, dtype=torch.int32, device=dev).reshape(self.nj, self.ni)
-        index = index.contiguous()
         tile = tuple(torch.empty((self.nj, self.ni), dtype=torch.float32, device=dev) for _ in range(3))
         need_max = slope_max is None or curv_max is None
         win = tuple(torch.empty_like(h) for _ in range(3)) if need_max else None
@@ -71,21 +68,12 @@ class WindTerrain:
             self._permute()
 
     def _permute(self):
-        torch = self.torch
-        dst = [torch.empty_like(t) for t in self.planes_tile]
-        torch.cuda.current_stream().synchronize()
-        self.engine.stream_sync()
-        self.engine.gather(dst, list(self.planes_tile), self.perm, self.ni, self.nj)()
-        self.engine.stream_sync()
-        self.planes = tuple(dst)
+        self.planes = tuple(permute_planes(self.engine, self.planes_tile, self.perm, self.ni, self.nj))
 
     def follow(self, store):
         """After Engine.sort_store(store): the three planes, permuted into the store's column order with noahmp_hip_gather_fields.  Waits for
         the engine's stream."""
-        perm = getattr(store, "sort_perm", None)
-        assert perm is not None, "follow() is for a store that Engine.sort_store has sorted"
-        assert store.ni == self.ni and store.nj == self.nj
-        self.perm = perm
+        self.perm = sorted_perm(store, self.ni, self.nj)
         if self.planes_tile is not None:
             self._permute()
 
