@@ -872,6 +872,36 @@ class Engine:
         before, adds its column's runoff and releases its fraction.  One kernel launch, enqueued only (noahmp_hip_route_runoff)."""
         self._call("noahmp_hip_route_runoff", C.byref(block), int(ncol), stream)
 
+    # ---- depression filling and flat resolution for the D8 network (noahmp_flow_fill.hip; helper: noahmp_amd/routing.py DepressionFill)
+    @staticmethod
+    def flow_fill_block(height, fixed, w_old, w_new, changed, eps, sweeps=1, flags=0, outlet=None):
+        """A noahmp_flow_fill block over the (nj, ni) WINDOW plane height (float32, device): fixed (and outlet, or None) uint8, w_old and
+        w_new float32 planes of the same shape, changed an int32 device word.  flags: NOAHMP_FILL_* bits (abi.FILL_FLAG).  The tensors
+        are kept alive by the returned block."""
+        import torch
+        assert height.dim() == 2 and height.is_contiguous() and height.dtype == torch.float32
+        for t, dt in ((fixed, torch.uint8), (w_old, torch.float32), (w_new, torch.float32)) + (((outlet, torch.uint8),) if outlet is not None else ()):
+            assert t.dtype == dt and t.is_contiguous() and t.numel() == height.numel()
+        assert changed.dtype == torch.int32 and changed.numel() >= 1
+        b = abi.FlowFill()
+        b.height, b.fixed, b.w_old, b.w_new, b.changed = (t.data_ptr() for t in (height, fixed, w_old, w_new, changed))
+        b.outlet = outlet.data_ptr() if outlet is not None else None
+        b.nj, b.ni = (int(v) for v in height.shape)
+        b.eps, b.sweeps, b.flags = float(eps), int(sweeps), int(flags)
+        b._keep = (height, fixed, w_old, w_new, changed, outlet)
+        return b
+
+    def flow_fill_init(self, block, stream=None):
+        """fixed and w_old of a block of Engine.flow_fill_block: outlets at their height, every other cell at +inf.  One kernel launch,
+        enqueued only (noahmp_hip_flow_fill_init)."""
+        self._call("noahmp_hip_flow_fill_init", C.byref(block), stream)
+
+    def flow_fill(self, block, stream=None):
+        """One call of the relaxation w_old -> w_new of a block of Engine.flow_fill_block: the pinned Jacobi pass (sweeps == 1) or the
+        tiled LDS kernel; the block's changed word receives 1 when a word differs.  One kernel launch, enqueued only
+        (noahmp_hip_flow_fill)."""
+        self._call("noahmp_hip_flow_fill", C.byref(block), stream)
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

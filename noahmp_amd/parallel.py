@@ -132,6 +132,11 @@ class Comm:
         self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
         return bool(t.item() > 0.0)
 
+    def agree_any(self, flag):
+        """True on every rank when `flag` is true on ANY rank (a MAX all-reduce over the control group); without a process group, the
+        flag itself.  Every rank must call it: DepressionFill.run ends its loop on it."""
+        return self._agree_any(flag) if self.dist else bool(flag)
+
     # ---- the engine's own exchange (C-ABI)
     def _halo_port(self, halo_port):
         return halo_port or int(os.environ.get("NMP_HALO_PORT", int(os.environ.get("MASTER_PORT", "29500")) + 1))

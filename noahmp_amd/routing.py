@@ -1,8 +1,11 @@
 """Discharge of a device-resident run: cell-to-cell linear reservoirs on a D8 network (noahmp_hip_flow_terrain / _flow_inmask /
-_flow_accumulate / noahmp_hip_route_runoff).
+_flow_accumulate / noahmp_hip_route_runoff), on raw terrain or on terrain conditioned on the device (noahmp_hip_flow_fill_init /
+noahmp_hip_flow_fill).
 
     net = FlowNetwork(engine, ni, nj)                              # the tile of the store
     net.set_terrain(height, dx, dy, origin=(i0, j0))               # once: height is a WINDOW = tile + 2 cells where there is a neighbour
+    #   or: net.set_terrain(height, dx, dy, fill=1e-3)             single tile: depressions filled, flats resolved first (net.filled)
+    #   or: net.set_terrain_filled(height_block, dx, dy, 1e-3, origin=(i0, j0), comm=comm, geom=geom)      the decomposed recipe
     #   or: net.set_directions(FlowNetwork.from_esri(codes), origin=(i0, j0), dx=dx, dy=dy)      codes: a window = tile + 1-cell ring
     net.set_area(area); net.set_velocity(0.5, dt)                  # m2 per cell; release = 1 - exp(-dt*v/length)
     net.follow(store)                                              # after Engine.sort_store: only col_index is rewritten
@@ -13,8 +16,14 @@ Every cell gathers what its upstream neighbours released in the call before, add
 and releases the fraction `release` of its storage; water leaves the network at the cells without a direction (outlets, pits, the coast).
 The window planes (the BLOCK: the tile plus a 1-cell ring where the window given has room for one) never move; a sorted store is followed
 through col_index alone.  Not represented: kinematic or diffusive wave, channel geometry, backwater, losses and lakes, a celerity above
-one cell per call (nsub sub-steps).  No pit filling, no flat resolution: a raw DEM is conditioned by the caller.  The contract -- every
-rounding -- is the text in include/noahmp_hip.h.
+one cell per call (nsub sub-steps).
+
+Conditioning a raw DEM (DepressionFill; set_terrain(fill=eps); set_terrain_filled): the surface W* of priority-flood + epsilon, made on the
+device as the fixed point of a monotone relaxation, the same bits in every schedule and every decomposition.  Built: every cell that can
+reach an outlet drains; flats and filled depressions become ramps of one lift (eps, or one float32 step where eps is below it) per cell
+away from their outlet.  Not built: carving / breaching, lakes with storage, a combined-gradient flat resolution (Garbrecht-Martz).
+Without fill, set_terrain takes the terrain as it is: water leaves the network at every pit.  The contract -- every rounding -- is the
+text in include/noahmp_hip.h.
 """
 import math
 
@@ -24,6 +33,113 @@ from .tile import check_window, inverse_perm, sorted_perm, window_index
 
 ESRI_CODES = {1: 1, 128: 2, 64: 3, 32: 4, 16: 5, 8: 6, 4: 7, 2: 8}      # ESRI / WRF-Hydro FLOWDIRECTION (E = 1, clockwise) -> k, with j towards north
 NOT_OWNED = -2                                                           # col_index of a ring cell
+# in-tile sweeps per call of noahmp_hip_flow_fill, from profiles/flow_fill_bench.md (tools/flow_fill_bench.py, one MI355X, device time
+# to the fixed point): 16 is the fastest setting at 7 077 888 cells (3.13 ms; 4: 3.41, 64: 3.31, pinned: 46.4) and second at 884 736 cells
+# (1.03 ms; 4: 0.85, 64: 1.15, pinned: 5.21).  No setting is fastest at both sizes; 16 has the smallest sum over the two.
+FILL_SWEEPS = 16
+
+
+class DepressionFill:
+    """The filled surface W* of a height window (noahmp_hip_flow_fill_init / noahmp_hip_flow_fill).
+
+        fill = DepressionFill(engine)
+        fill.begin(height, eps)                  # every window edge an outlet side
+        w = fill.run()                           # calls until one changes nothing; fill.calls counts them
+    """
+
+    def __init__(self, engine):
+        import torch
+        self.engine, self.torch = engine, torch
+        self.height = self.fixed = self.outlet = None
+        self.w, self.cur = None, 0
+        self.flags = self.eps = None
+        self.changed = None                                              # two device words: [0] the calls before the last of a relax(), [1] the last
+        self.free_cells = self.calls = 0
+        self._blocks = {}
+
+    @staticmethod
+    def _side_flags(outlet_sides, ring_sides):
+        from . import abi
+        f = 0
+        for kind, sides in (("outlet", outlet_sides), ("ring", ring_sides)):
+            for s in sides.lower():
+                if s not in "wesn":
+                    raise ValueError("sides are letters of 'wesn', not %r" % s)
+                f |= abi.FILL_FLAG["%s_%s" % (kind, s)]
+        return f
+
+    def begin(self, height_window, eps, outlet=None, outlet_sides="wesn", ring_sides=""):
+        """height_window: (nj, ni) float32 device plane [m].  eps: the lift increment [m].  outlet: uint8 plane, non-zero = a caller
+        outlet, or None.  outlet_sides / ring_sides: letters of "wesn"; a side in neither is a closed wall.  One launch; w is z at the
+        outlets and +inf elsewhere, a ring waits for the caller's exchange."""
+        torch = self.torch
+        assert height_window.dim() == 2
+        self.height = height_window.to(torch.float32).contiguous()
+        dev = self.height.device
+        self.outlet = None if outlet is None else (outlet != 0).to(torch.uint8).contiguous()
+        self.fixed = torch.empty(self.height.shape, dtype=torch.uint8, device=dev)
+        self.w, self.cur = [torch.empty_like(self.height), torch.empty_like(self.height)], 0
+        self.changed = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.flags, self.eps = self._side_flags(outlet_sides, ring_sides), float(eps)
+        self._blocks = {}
+        torch.cuda.current_stream().synchronize()
+        self.engine.flow_fill_init(self._block(0, 0, 1))
+        self.engine.stream_sync()
+        self.free_cells = int((self.fixed == 0).sum().item())
+        self.calls = 0
+
+    def _block(self, cur, word, sweeps):
+        key = (cur, word, sweeps)
+        b = self._blocks.get(key)
+        if b is None:
+            b = self._blocks[key] = self.engine.flow_fill_block(self.height, self.fixed, self.w[cur], self.w[1 - cur], self.changed[word:word + 1],
+                                                                self.eps, sweeps=sweeps, flags=self.flags, outlet=self.outlet)
+        return b
+
+    @property
+    def surface(self):
+        """The current plane w (W* once a call has changed nothing)."""
+        return self.w[self.cur]
+
+    def relax(self, ncall=1, sweeps=None):
+        """ncall calls of noahmp_hip_flow_fill, enqueued in a row, ping-ponging the two planes; returns the LAST call's flag (0: it changed
+        nothing, the surface is W*).  The last call stores into a flag word of its own, zeroed with the other before the batch, so there
+        is one host wait per relax(), not one per call."""
+        torch = self.torch
+        sweeps = FILL_SWEEPS if sweeps is None else int(sweeps)
+        assert ncall >= 1 and self.w is not None
+        self.changed.zero_()
+        torch.cuda.current_stream().synchronize()
+        for n in range(int(ncall)):
+            self.engine.flow_fill(self._block(self.cur, 1 if n == ncall - 1 else 0, sweeps))
+            self.cur = 1 - self.cur
+        self.engine.stream_sync()
+        self.calls += int(ncall)
+        return int(self.changed[1].item())
+
+    def run(self, max_call=None, check=8, sweeps=None, comm=None, geom=None):
+        """Calls until one changes nothing; returns the surface W*.  The flag is read every `check` calls.  max_call defaults to the number
+        of free cells + 1 (every call lowers at least the cells a Jacobi pass lowers, and a Jacobi pass that lowers anything brings at
+        least one more cell to its final value); exceeding it raises.
+        With a comm (the window is the block: the tile plus the ring sides given to begin()), EVERY call is preceded by
+        comm.exchange_halo([w], geom) and followed by comm.agree_any(flag): the loop ends when no rank changed anything in a call that
+        followed an exchange.  max_call is then the caller's, the same number on every rank (None: no limit; the loop ends by the
+        argument in DESIGN.md section 6).  THE STREAM RULE of FlowNetwork.step holds: the exchange runs on torch's current stream, the
+        launches on the engine's; each waits for the other."""
+        torch = self.torch
+        if comm is None:
+            max_call = self.free_cells + 1 if max_call is None else int(max_call)
+            while self.calls < max_call:
+                if self.relax(min(int(check), max_call - self.calls), sweeps) == 0:
+                    return self.surface
+            raise RuntimeError("DepressionFill.run: still changing after %d calls" % self.calls)
+        while max_call is None or self.calls < int(max_call):
+            self.engine.stream_sync()                                    # w is written before it travels
+            comm.exchange_halo([self.surface], geom)
+            torch.cuda.current_stream().synchronize()                    # ... and its ring has arrived before the call reads it
+            if not comm.agree_any(self.relax(1, sweeps) != 0):
+                return self.surface
+        raise RuntimeError("DepressionFill.run: still changing on some rank after %d calls" % self.calls)
 
 
 class FlowNetwork:
@@ -45,6 +161,8 @@ class FlowNetwork:
         self.last_dt = None
         self.passes = 0                                                  # passes the last upstream_cells() made
         self._area_default = True                                        # area is dx*dy of the last set_directions, not the caller's
+        self.filled = None                                               # the filled height plane of set_terrain(fill=...) / set_terrain_filled
+        self.fill_calls = 0                                              # calls of noahmp_hip_flow_fill it took
 
     # ---- the network
     @staticmethod
@@ -69,17 +187,57 @@ class FlowNetwork:
         e, n = min(1, ni_w - i0 - self.ni), min(1, nj_w - j0 - self.nj)
         return (slice(j0 - s, j0 + self.nj + n), slice(i0 - w, i0 + self.ni + e)), (w, s)
 
-    def set_terrain(self, height, dx, dy, origin=(0, 0)):
+    def set_terrain(self, height, dx, dy, origin=(0, 0), fill=None, outlet=None):
         """height: the terrain height [m] of an (nj_w, ni_w) float32 device WINDOW that contains the tile with its cell (0, 0) at window
         cell origin = (i0, j0): the tile plus 2 cells on every side that is not an edge of the whole domain gives, on the block, the
-        directions of the undecomposed run.  Two launches, once."""
+        directions of the undecomposed run.  Two launches, once.
+        fill = eps [m]: SINGLE-TILE conditioning.  The window is filled first (DepressionFill, every window edge an outlet side, `outlet`
+        an optional uint8 plane of caller outlets) and the directions are those of the filled plane, kept as self.filled.  A filled
+        surface is global: a decomposed caller uses set_terrain_filled."""
         torch = self.torch
         assert height.dim() == 2
         h = height.to(torch.float32).contiguous()
+        self.filled = None
+        if fill is not None:
+            f = DepressionFill(self.engine)
+            f.begin(h, fill, outlet=outlet)
+            h = self.filled = f.run()
+            self.fill_calls = f.calls
         d = torch.empty(h.shape, dtype=torch.uint8, device=h.device)
         torch.cuda.current_stream().synchronize()
         self.engine.flow_terrain(self.engine.flow_terrain_block(h, d, dx, dy))
         self.engine.stream_sync()
+        self.set_directions(d, origin=origin, dx=dx, dy=dy)
+
+    def set_terrain_filled(self, height_block, dx, dy, eps, origin=(0, 0), outlet=None, comm=None, geom=None):
+        """The decomposed recipe.  height_block: the terrain height [m] of the BLOCK, the tile plus a 1-cell
+        ring on every side where a neighbour rank exists, the tile's cell (0, 0) at block cell origin = (i0, j0).  Sides with a ring are
+        RING sides of the fill, the others OUTLET sides.  (1) fill on the block, (2) the ring of w exchanged before every call
+        (DepressionFill.run), (3) noahmp_hip_flow_terrain on the filled block -- right on the tile's cells, (4) the ring's directions
+        through the same exchange as a float32 plane (0..8 are exact), (5) set_directions.  The filled block is kept as self.filled."""
+        torch = self.torch
+        assert height_block.dim() == 2
+        i0, j0 = check_window(tuple(height_block.shape), origin, self.ni, self.nj)
+        nj_b, ni_b = height_block.shape
+        room = dict(w=i0, e=ni_b - i0 - self.ni, s=j0, n=nj_b - j0 - self.nj)
+        if any(v not in (0, 1) for v in room.values()):
+            raise ValueError("set_terrain_filled takes the block: the tile plus a ring of ONE cell where there is a neighbour")
+        ring = "".join(k for k, v in room.items() if v == 1)
+        if ring and comm is None:
+            raise ValueError("a block with a ring needs the comm that fills it")
+        f = DepressionFill(self.engine)
+        f.begin(height_block, eps, outlet=outlet, outlet_sides="".join(k for k in "wesn" if k not in ring), ring_sides=ring)
+        self.filled = f.run(comm=comm, geom=geom) if ring else f.run()
+        self.fill_calls = f.calls
+        d = torch.empty(self.filled.shape, dtype=torch.uint8, device=self.filled.device)
+        torch.cuda.current_stream().synchronize()
+        self.engine.flow_terrain(self.engine.flow_terrain_block(self.filled, d, dx, dy))
+        self.engine.stream_sync()
+        if ring:
+            df = d.to(torch.float32)
+            comm.exchange_halo([df], geom)
+            torch.cuda.current_stream().synchronize()
+            d = df.to(torch.uint8)
         self.set_directions(d, origin=origin, dx=dx, dy=dy)
 
     def set_directions(self, dir_window, origin=(0, 0), dx=None, dy=None):
