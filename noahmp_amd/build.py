@@ -14,7 +14,8 @@ SOURCES = ["noahmp_engine.hip", "noahmp_groundwater.hip", "noahmp_init.hip", "no
            "noahmp_engine_d3_r1.hip", "noahmp_engine_d3_r5.hip", "noahmp_engine_d4_r1.hip", "noahmp_engine_d4_r3.hip",
            "noahmp_jit.hip", "noahmp_sort.hip", "noahmp_halo.hip", "noahmp_stage.hip", "noahmp_history.hip", "noahmp_regions.hip",
            "noahmp_regrid.hip", "noahmp_shortwave.hip", "noahmp_regrid_conserve.hip", "noahmp_shadow.hip",
-           "noahmp_skyview.hip", "noahmp_wind.hip", "noahmp_routing.hip", "noahmp_flow_fill.hip"]
+           "noahmp_skyview.hip", "noahmp_wind.hip", "noahmp_routing.hip", "noahmp_flow_fill.hip",
+           "noahmp_basins.hip"]
 
 
 def _headers():

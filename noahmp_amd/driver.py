@@ -902,6 +902,42 @@ class Engine:
         (noahmp_hip_flow_fill)."""
         self._call("noahmp_hip_flow_fill", C.byref(block), stream)
 
+    # ---- watershed delineation on the D8 network (noahmp_basins.hip; helper: noahmp_amd/routing.py Basins)
+    @staticmethod
+    def flow_basin_block(dir, state_old, state_new, label, dist, changed, flags=0, seed=None, sweeps=1):
+        """A noahmp_flow_basin block over the (nj, ni) WINDOW plane dir (uint8, device): state_old and state_new int64 planes (one packed
+        {int32 ptr, int32 hops} word per cell), label, dist (and seed, or None) int32 planes of the same shape, changed an int32 device
+        word.  flags: NOAHMP_BASIN_RING_* bits (abi.BASIN_FLAG).  sweeps: 1 = the pinned pass, more = the tiled form of the pass.  The tensors
+        are kept alive by the returned block."""
+        import torch
+        assert dir.dim() == 2 and dir.is_contiguous() and dir.dtype == torch.uint8
+        for t, dt in ((state_old, torch.int64), (state_new, torch.int64), (label, torch.int32), (dist, torch.int32)) + (((seed, torch.int32),) if seed is not None else ()):
+            assert t.dtype == dt and t.is_contiguous() and t.numel() == dir.numel()
+        assert changed.dtype == torch.int32 and changed.numel() >= 1
+        b = abi.FlowBasin()
+        b.dir, b.state_old, b.state_new, b.label, b.dist, b.changed = (t.data_ptr() for t in (dir, state_old, state_new, label, dist, changed))
+        b.seed = seed.data_ptr() if seed is not None else None
+        b.nj, b.ni = (int(v) for v in dir.shape)
+        b.flags, b.sweeps = int(flags), int(sweeps)
+        b._keep = (dir, state_old, state_new, label, dist, changed, seed)
+        return b
+
+    def flow_basin_init(self, block, stream=None):
+        """state_old, label and dist of a block of Engine.flow_basin_block: every cell points at its downstream cell, roots (gauges, cells
+        without a downstream cell, ring cells) at themselves.  One kernel launch, enqueued only (noahmp_hip_flow_basin_init)."""
+        self._call("noahmp_hip_flow_basin_init", C.byref(block), stream)
+
+    def flow_basin_jump(self, block, stream=None):
+        """One doubling pass state_old -> state_new (the block's sweeps: the pinned pass, or the tiled form that first contracts the paths
+        inside every 64 x 32 tile); the block's changed word receives 1 when a pointer moved.  One kernel launch, enqueued only
+        (noahmp_hip_flow_basin_jump)."""
+        self._call("noahmp_hip_flow_basin_jump", C.byref(block), stream)
+
+    def flow_basin_resolve(self, block, stream=None):
+        """label and dist of every cell from its root's, in place, on the converged state_old of the block; changed receives 1 when a
+        label changed.  One kernel launch, enqueued only (noahmp_hip_flow_basin_resolve)."""
+        self._call("noahmp_hip_flow_basin_resolve", C.byref(block), stream)
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

@@ -1,6 +1,6 @@
 """Discharge of a device-resident run: cell-to-cell linear reservoirs on a D8 network (noahmp_hip_flow_terrain / _flow_inmask /
 _flow_accumulate / noahmp_hip_route_runoff), on raw terrain or on terrain conditioned on the device (noahmp_hip_flow_fill_init /
-noahmp_hip_flow_fill).
+noahmp_hip_flow_fill), and the basins of gauge cells on that network (noahmp_hip_flow_basin_init / _jump / _resolve; class Basins below).
 
     net = FlowNetwork(engine, ni, nj)                              # the tile of the store
     net.set_terrain(height, dx, dy, origin=(i0, j0))               # once: height is a WINDOW = tile + 2 cells where there is a neighbour
@@ -302,7 +302,9 @@ class FlowNetwork:
     def upstream_cells(self, max_pass=None):
         """The number of cells that drain through every cell of the block, itself included (uint32 words in an int32 device plane):
         noahmp_hip_flow_accumulate until nothing changes, the flag read every 64 passes.  SINGLE-TILE: the block's edge counts as the
-        domain's; a decomposed caller exchanges acc after every pass and agrees on `changed` itself.  max_pass defaults to 4*(ni + nj)."""
+        domain's; a decomposed caller exchanges acc after every pass and agrees on `changed` itself.  max_pass defaults to 4*(ni + nj).
+        It needs one pass per cell of the longest flow path: Basins(net).run() gives that length (hops.max() + 1) in a logarithmic number
+        of launches."""
         torch = self.torch
         nj, ni = self.block_shape
         max_pass = 4 * (ni + nj) if max_pass is None else int(max_pass)
@@ -415,3 +417,243 @@ class FlowNetwork:
         self.storage.copy_(state["storage"])
         self.out[self.cur].copy_(state["out"])
         self.torch.cuda.current_stream().synchronize()
+
+
+BASIN_CHECK = 4                                                          # jump passes enqueued between two host waits
+# in-tile iterations of the FIRST call of noahmp_hip_flow_basin_jump, which is then the tiled form; the calls after it are pinned passes.
+# From profiles/basins_bench.md (tools/basins_bench.py, one MI355X, device time of the calls to the fixed point): on the filled terrain 9
+# calls in 0.261 ms against 12 pinned passes in 0.359 ms at 7 077 888 cells and 8 in 0.052 against 11 in 0.076 ms at 884 736; on the raw
+# terrain 4 against 5 calls, 0.155 / 0.164 and 0.037 / 0.038 ms.  The tiled form in EVERY call saves no further call and costs more per
+# call (0.387 and 0.080 ms on the filled terrain).  12 = the 11 doublings a path inside a 64 x 32 tile can need and the one that moves nothing.
+BASIN_SWEEPS = 12
+
+
+class Basins:
+    """Which gauge every cell of a FlowNetwork drains to, and how many cells away it is (noahmp_hip_flow_basin_init / _jump / _resolve):
+    pointer doubling over the directions, ceil(log2 L) + 1 passes for a longest flow path of L cells.
+
+        b = Basins(net)                          # a FlowNetwork with directions set; works on its block
+        b.set_gauges([(i, j), ...])              # tile cells -> ids 0..n-1; or a block-shaped int32 seed plane (>= 0: a gauge's id)
+        #   or: b.set_outlet_gauges()            single tile: every tile cell without a downstream cell, row-major ids
+        b.run()                                  # decomposed: b.run(comm=comm, geom=geom)
+        b.label, b.hops                          # int32 block planes; b.passes, b.rounds
+        rg = Regions(engine, store, b.region_map(), b.ngauge)
+
+    A gauge cell is the root of its INCREMENTAL area: cells above another gauge belong to that one.  downstream_gauge() and nested() turn
+    incremental sums into whole-basin sums on the host.  label is the gauge's id, or NOAHMP_BASIN_NONE (-1: the path ends at a cell without
+    a downstream cell that is no gauge), _PENDING (-2: it ends in a ring nobody answered for, or on a cycle across ranks), _CYCLE (-3: it
+    ends on a cycle of caller-given directions).  hops counts the cells to the gauge or outlet, -1 where there is none.  Integer words and
+    a unique fixed point: the same planes in every schedule and every decomposition.  Not represented: weighted or metric flow length."""
+
+    def __init__(self, net):
+        if net.dir is None:
+            raise ValueError("the FlowNetwork has no directions: call set_terrain() or set_directions() first")
+        self.net, self.engine, self.torch = net, net.engine, net.torch
+        self.seed, self.ngauge = None, 0
+        self.label = self.hops = self.state = self.changed = None
+        self.cur = self.passes = self.rounds = 0
+        self.cap = (max(net.dir.numel(), 1) - 1).bit_length() + 1          # ceil(log2(ni*nj)) + 1
+        self._blocks = {}
+        self._moved = None
+
+    # ---- gauges
+    def _block_dir(self):
+        return self.net.dir.cpu().numpy()
+
+    def set_gauges(self, points):
+        """points: [(i, j)] in TILE cells, ids 0..n-1 in the order given; or an int32 plane of the block (numpy or device), >= 0 = the id
+        of the gauge at that cell (a decomposed caller gives ids that mean the same on every rank), negative = none."""
+        torch, net = self.torch, self.net
+        dev = net.dir.device
+        if torch.is_tensor(points) or (isinstance(points, np.ndarray) and points.ndim == 2 and tuple(points.shape) == net.block_shape):
+            seed = torch.as_tensor(points, device=dev).to(torch.int32).contiguous()
+            assert tuple(seed.shape) == net.block_shape, "a seed plane has the shape of the block %s" % (net.block_shape,)
+            self.ngauge = max(0, int(seed.max().item()) + 1) if seed.numel() else 0
+        else:
+            pts = [(int(i), int(j)) for i, j in points]
+            if len(set(pts)) != len(pts):
+                raise ValueError("two gauges at one cell")
+            plane = np.full(net.block_shape, -1, np.int32)
+            for n, (i, j) in enumerate(pts):
+                if not (0 <= i < net.ni and 0 <= j < net.nj):
+                    raise ValueError("gauge %d at (%d, %d) lies outside the tile %d x %d" % (n, i, j, net.ni, net.nj))
+                plane[net.j0 + j, net.i0 + i] = n
+            seed = torch.from_numpy(plane).to(dev)
+            self.ngauge = len(pts)
+        self.seed = seed if self.ngauge else None
+        self._blocks = {}
+
+    def set_outlet_gauges(self):
+        """SINGLE TILE: every tile cell without a downstream cell (no direction, or one that leaves the block) becomes a gauge; ids in
+        row-major order of the tile.  Returns their (i, j)."""
+        net = self.net
+        down = _np_down(self._block_dir())
+        tile = down[net.j0:net.j0 + net.nj, net.i0:net.i0 + net.ni]
+        jj, ii = np.nonzero(tile < 0)
+        pts = list(zip(ii.tolist(), jj.tolist()))
+        self.set_gauges(pts)
+        return pts
+
+    # ---- the calls
+    def ring_sides(self):
+        """The sides of the block that are a ring: letters of "wesn"."""
+        net = self.net
+        nj, ni = net.block_shape
+        room = dict(w=net.i0, e=ni - net.i0 - net.ni, s=net.j0, n=nj - net.j0 - net.nj)
+        return "".join(k for k, v in room.items() if v == 1)
+
+    def _block(self, cur, word, sweeps=1):
+        key = (cur, word, sweeps)
+        b = self._blocks.get(key)
+        if b is None:
+            from . import abi
+            flags = sum(abi.BASIN_FLAG["ring_" + s] for s in self.ring_sides())
+            b = self._blocks[key] = self.engine.flow_basin_block(self.net.dir, self.state[cur], self.state[1 - cur], self.label, self.hops,
+                                                                 self.changed[word:word + 1], flags=flags, seed=self.seed, sweeps=sweeps)
+        return b
+
+    def begin(self):
+        """The planes and noahmp_hip_flow_basin_init: one launch."""
+        torch = self.torch
+        shape, dev = self.net.block_shape, self.net.dir.device
+        self.state = [torch.empty(shape, dtype=torch.int64, device=dev), torch.empty(shape, dtype=torch.int64, device=dev)]
+        self.label = torch.empty(shape, dtype=torch.int32, device=dev)
+        self.hops = torch.empty(shape, dtype=torch.int32, device=dev)
+        self.changed = torch.zeros(self.cap + 1, dtype=torch.int32, device=dev)      # a word per pass, the last for resolve
+        self.cur = self.passes = self.rounds = 0
+        self._blocks = {}
+        torch.cuda.current_stream().synchronize()
+        self.engine.flow_basin_init(self._block(0, 0))
+        self.engine.stream_sync()
+
+    def contract(self, check=BASIN_CHECK, sweeps=None, tiled_calls=1):
+        """noahmp_hip_flow_basin_jump until a pass moves no pointer or the cap of ceil(log2(ni*nj)) + 1 passes: `check` passes are enqueued in
+        a row, each with a flag word of its own, and the host waits once per batch.  self.passes: the passes up to and including the first
+        that changed nothing (a batch may have made up to check - 1 more: they change nothing either).  Returns True when it converged,
+        False at the cap: caller-given directions hold a cycle, which resolve() marks.
+        sweeps > 1: the first `tiled_calls` calls (None: all of them) are the tiled form with that many in-tile iterations; it moves every
+        pointer at least as far as the pinned pass, so the cap holds."""
+        torch = self.torch
+        sweeps = BASIN_SWEEPS if sweeps is None else int(sweeps)
+        self.changed.zero_()
+        torch.cuda.current_stream().synchronize()
+        done = 0
+        while done < self.cap:
+            n = min(int(check), self.cap - done)
+            for k in range(done, done + n):
+                self.engine.flow_basin_jump(self._block(self.cur, k, sweeps if tiled_calls is None or k < tiled_calls else 1))
+                self.cur = 1 - self.cur
+            self.engine.stream_sync()
+            flags = self.changed[done:done + n].cpu().numpy()
+            done += n
+            still = np.nonzero(flags == 0)[0]
+            if still.size:
+                self.passes = done - n + int(still[0]) + 1
+                return True
+        self.passes = done
+        return False
+
+    def resolve(self):
+        """One noahmp_hip_flow_basin_resolve on the contracted state; returns its flag (0: no label changed)."""
+        torch = self.torch
+        self.changed[self.cap:].zero_()
+        torch.cuda.current_stream().synchronize()
+        self.engine.flow_basin_resolve(self._block(self.cur, self.cap))
+        self.engine.stream_sync()
+        self.rounds += 1
+        return int(self.changed[self.cap].item())
+
+    def unresolved(self):
+        """(cells of the tile labelled CYCLE, cells of the tile labelled PENDING)."""
+        from . import abi
+        t = self.net.tile_view(self.label)
+        return int((t == abi.BASIN_CYCLE).sum().item()), int((t == abi.BASIN_PENDING).sum().item())
+
+    def run(self, comm=None, geom=None, strict=True, check=BASIN_CHECK, sweeps=None, tiled_calls=1):
+        """init, the doubling passes, and the resolve rounds: one without a comm; with a comm (the block's ring sides are owned by
+        neighbour ranks) { comm.exchange_halo of label and hops, resolve, comm.agree_any(changed) } until no rank changed anything -- the
+        largest number of ownership changes along a flow path, plus 2, rounds.  The passes stay local: ring cells are roots.  The int32
+        planes travel as float32 views of the same words (every mover copies words).
+        THE STREAM RULE of FlowNetwork.step holds: the exchange runs on torch's current stream, the launches on the engine's; each waits
+        for the other.
+        strict: a tile cell that ends as CYCLE or PENDING raises RuntimeError with the counts; strict=False leaves them marked.
+        check, sweeps, tiled_calls: those of contract()."""
+        torch = self.torch
+        ring = self.ring_sides()
+        if ring and comm is None:
+            raise ValueError("a block with a ring needs the comm that fills it")
+        self.begin()
+        self.contract(check, sweeps, tiled_calls)
+        if comm is None:
+            self.resolve()
+        else:
+            views = [self.label.view(torch.float32), self.hops.view(torch.float32)]
+            while True:
+                self.engine.stream_sync()                                # label and hops are written before they travel
+                comm.exchange_halo(views, geom)
+                torch.cuda.current_stream().synchronize()                # ... and their ring has arrived before resolve reads it
+                if not comm.agree_any(self.resolve() != 0):
+                    break
+        if strict:
+            ncycle, npending = self.unresolved()
+            if ncycle or npending:
+                raise RuntimeError("Basins.run: %d cells of the tile end on a cycle of the directions and %d are pending (a ring nobody "
+                                   "answered for, or a cycle across ranks)" % (ncycle, npending))
+        return self.label
+
+    # ---- what comes out
+    def region_map(self):
+        """int32 (nj, ni) in TILE order, the gauge's id or a negative word: the region_map of Regions (nregion = self.ngauge)."""
+        return self.net.tile_view(self.label).contiguous().clone()
+
+    def gauge_cells(self):
+        """Block cell (j, i) of every gauge, int64 [ngauge, 2]; every id must mark exactly one cell."""
+        out = np.full((self.ngauge, 2), -1, np.int64)
+        if self.ngauge:
+            seed = self.seed.cpu().numpy()
+            jj, ii = np.nonzero(seed >= 0)
+            ids = seed[jj, ii]
+            if len(np.unique(ids)) != len(ids) or len(ids) != self.ngauge:
+                raise ValueError("downstream_gauge needs ids 0..n-1 with one cell each")
+            out[ids, 0], out[ids, 1] = jj, ii
+        return out
+
+    def downstream_gauge(self):
+        """Per gauge the label of the cell below it: the next gauge downstream, or -1 (none: it drains to an outlet that is no gauge, has
+        no downstream cell, or the cell below is unresolved).  int32 [ngauge], after run()."""
+        cells = self.gauge_cells()
+        down = _np_down(self._block_dir())
+        label = self.label.cpu().numpy().ravel()
+        out = np.full(self.ngauge, -1, np.int32)
+        for g, (j, i) in enumerate(cells):
+            d = down[j, i]
+            if d >= 0 and label[d] >= 0:
+                out[g] = label[d]
+        return out
+
+    def nested(self, series):
+        """series[..., g]: sums over the INCREMENTAL area of gauge g (what Regions gives for region_map()).  Returns the sums over the whole
+        basin above every gauge: every gauge's own value added to every gauge downstream of it."""
+        dg = self.downstream_gauge()
+        inc = np.array(series)
+        assert inc.shape[-1] == self.ngauge
+        out = inc.copy()
+        for g in range(self.ngauge):
+            d, n = dg[g], 0
+            while d >= 0:
+                out[..., d] += inc[..., g]
+                d, n = dg[d], n + 1
+                assert n <= self.ngauge, "downstream_gauge holds a cycle"
+        return out
+
+
+def _np_down(d):
+    """down(c) of the header text over a block of directions: the flat index of the downstream cell, -1 where there is none."""
+    nj, ni = d.shape
+    k = np.where(d <= 8, d, 0).astype(np.int64)
+    di = np.array((0, 1, 1, 0, -1, -1, -1, 0, 1))[k]
+    dj = np.array((0, 0, 1, 1, 1, 0, -1, -1, -1))[k]
+    jj, ii = np.meshgrid(np.arange(nj), np.arange(ni), indexing="ij")
+    jn, i_n = jj + dj, ii + di
+    ok = (k > 0) & (jn >= 0) & (jn < nj) & (i_n >= 0) & (i_n < ni)
+    return np.where(ok, jn * ni + i_n, -1)
