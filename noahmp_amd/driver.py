@@ -938,6 +938,43 @@ class Engine:
         label changed.  One kernel launch, enqueued only (noahmp_hip_flow_basin_resolve)."""
         self._call("noahmp_hip_flow_basin_resolve", C.byref(block), stream)
 
+    # ---- upstream sums on the D8 network (noahmp_accum.hip; helper: noahmp_amd/routing.py Upstream)
+    @staticmethod
+    def flow_upstream_block(dir, sum, pend_in, pend_out, jump_old, jump_new, changed, flags=0, weight=None, inflow=None):
+        """A noahmp_flow_upstream block over the (nj, ni) WINDOW plane dir (uint8, device): sum, pend_in and pend_out (and inflow, or
+        None) int64 planes of the same shape holding uint64 words, jump_old and jump_new (and weight, or None: uint32 words) int32 planes,
+        changed an int32 device word.  flags: NOAHMP_UPSTREAM_RING_* bits (abi.UPSTREAM_FLAG).  The tensors are kept alive by the
+        returned block."""
+        import torch
+        assert dir.dim() == 2 and dir.is_contiguous() and dir.dtype == torch.uint8
+        planes = ((sum, torch.int64), (pend_in, torch.int64), (pend_out, torch.int64), (jump_old, torch.int32), (jump_new, torch.int32))
+        planes += ((weight, torch.int32),) if weight is not None else ()
+        planes += ((inflow, torch.int64),) if inflow is not None else ()
+        for t, dt in planes:
+            assert t.dtype == dt and t.is_contiguous() and t.numel() == dir.numel()
+        assert changed.dtype == torch.int32 and changed.numel() >= 1
+        b = abi.FlowUpstream()
+        b.dir, b.sum, b.pend_in, b.pend_out, b.jump_old, b.jump_new, b.changed = (
+            t.data_ptr() for t in (dir, sum, pend_in, pend_out, jump_old, jump_new, changed))
+        b.weight = weight.data_ptr() if weight is not None else None
+        b.inflow = inflow.data_ptr() if inflow is not None else None
+        b.nj, b.ni = (int(v) for v in dir.shape)
+        b.flags = int(flags)
+        b._keep = (dir, sum, pend_in, pend_out, jump_old, jump_new, changed, weight, inflow)
+        return b
+
+    def flow_upstream_init(self, block, stream=None):
+        """sum, pend_in, pend_out and jump_old of a block of Engine.flow_upstream_block: every cell holds its weight (a ring cell its
+        inflow) and jumps to its downstream cell; edges into ring cells are cut.  One kernel launch, enqueued only
+        (noahmp_hip_flow_upstream_init)."""
+        self._call("noahmp_hip_flow_upstream_init", C.byref(block), stream)
+
+    def flow_upstream_pass(self, block, stream=None):
+        """One doubling pass: every cell folds pend_in into sum, pushes the sum to pend_out at its jump and squares the jump into
+        jump_new; the block's changed word receives 1 when a cell pushed.  The caller swaps the jump planes and the pend planes between
+        passes.  One kernel launch, enqueued only (noahmp_hip_flow_upstream_pass)."""
+        self._call("noahmp_hip_flow_upstream_pass", C.byref(block), stream)
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

@@ -1,6 +1,7 @@
 """Discharge of a device-resident run: cell-to-cell linear reservoirs on a D8 network (noahmp_hip_flow_terrain / _flow_inmask /
 _flow_accumulate / noahmp_hip_route_runoff), on raw terrain or on terrain conditioned on the device (noahmp_hip_flow_fill_init /
-noahmp_hip_flow_fill), and the basins of gauge cells on that network (noahmp_hip_flow_basin_init / _jump / _resolve; class Basins below).
+noahmp_hip_flow_fill), the basins of gauge cells on that network (noahmp_hip_flow_basin_init / _jump / _resolve; class Basins below)
+and the weighted upstream sums (noahmp_hip_flow_upstream_init / _pass; class Upstream below).
 
     net = FlowNetwork(engine, ni, nj)                              # the tile of the store
     net.set_terrain(height, dx, dy, origin=(i0, j0))               # once: height is a WINDOW = tile + 2 cells where there is a neighbour
@@ -657,3 +658,231 @@ def _np_down(d):
     jn, i_n = jj + dj, ii + di
     ok = (k > 0) & (jn >= 0) & (jn < nj) & (i_n >= 0) & (i_n < ni)
     return np.where(ok, jn * ni + i_n, -1)
+
+
+UPSTREAM_CHECK = 4                                                       # passes enqueued between two host waits
+
+
+class Upstream:
+    """The sum of a weight over the cells that drain through every cell of a FlowNetwork, itself included (noahmp_hip_flow_upstream_init /
+    _pass): the drained cell count, or the contributing area, by doubling -- bit_length(L) + 1 passes for a longest flow path of L hops.
+
+        u = Upstream(net)                        # a FlowNetwork with directions set; works on its block
+        u.set_weight(Upstream.quantise(area, 100.0))     # uint32 words (here: units of 100 m2), block-shaped; None = 1 everywhere
+        s = u.run()                              # decomposed: u.run(comm=comm, geom=geom); u.sum is the same plane
+        u.channel_mask(5000)                     # bool: sum >= threshold
+        u.passes, u.rounds, u.converged
+
+    Words are uint64, kept in an int64 plane: a legal sum is below 2^63.  The adds are integer adds, so every schedule and every
+    decomposition gives the same words; a real-valued weight is quantised ONCE, on the host side (quantise).  Not represented: float
+    accumulation, metric flow length, Strahler order.
+    A cycle of caller-given directions keeps the passes pushing up to the cap of ceil(log2(ni*nj)) + 1: run(strict=True) raises;
+    strict=False sets converged = False and leaves the sums, exact wherever the cell is not on a cycle, for the caller to mask with the
+    CYCLE labels of Basins."""
+
+    def __init__(self, net):
+        if net.dir is None:
+            raise ValueError("the FlowNetwork has no directions: call set_terrain() or set_directions() first")
+        self.net, self.engine, self.torch = net, net.engine, net.torch
+        self.weight = None
+        self._sum = self.pend = self.jump = self.changed = self.inflow = None
+        self._ring = self._feeds = self._halo = None
+        self.cur = self.passes = self.rounds = 0
+        self.converged = False
+        self.cap = (max(net.dir.numel(), 1) - 1).bit_length() + 1          # ceil(log2(ni*nj)) + 1
+        self._blocks = {}
+
+    # ---- the weight
+    def set_weight(self, plane=None):
+        """plane: uint32 words of the block -- an int32 device plane read as uint32, or a numpy uint32 / int32 array -- or None for 1
+        at every cell.  Weights of ring cells are not read (their owner counts them)."""
+        torch = self.torch
+        if plane is not None:
+            if isinstance(plane, np.ndarray):
+                assert plane.dtype in (np.uint32, np.int32), "weights are uint32 words: Upstream.quantise makes them"
+                plane = torch.from_numpy(np.ascontiguousarray(plane).view(np.int32))
+            assert plane.dtype == torch.int32 and tuple(plane.shape) == self.net.block_shape, \
+                "a weight plane is int32 (uint32 words) and has the shape of the block %s" % (self.net.block_shape,)
+            plane = plane.to(self.net.dir.device).contiguous()
+        self.weight = plane
+        self._blocks = {}
+
+    @staticmethod
+    def quantise(field, step):
+        """round(field / step) as uint32 words, made in float64, ties to even: a numpy array gives a numpy uint32 array, a tensor an int32
+        tensor holding the same words.  Raises ValueError on a NaN, a negative value or a quotient above 2^32 - 1."""
+        is_np = isinstance(field, np.ndarray) or not hasattr(field, "cpu")
+        q = np.rint(np.asarray(field if is_np else field.cpu().numpy(), np.float64) / float(step))
+        if np.isnan(q).any():
+            raise ValueError("Upstream.quantise: the field holds a NaN (or step is 0 or NaN)")
+        if (q < 0).any():
+            raise ValueError("Upstream.quantise: negative values cannot be weights")
+        if (q > 4294967295.0).any():
+            raise ValueError("Upstream.quantise: a value above (2^32 - 1) * step; choose a larger step")
+        w = q.astype(np.uint32)
+        if is_np:
+            return w
+        import torch
+        return torch.from_numpy(w.view(np.int32)).to(field.device)
+
+    # ---- the calls
+    def ring_sides(self):
+        """The sides of the block that are a ring: letters of "wesn"."""
+        net = self.net
+        nj, ni = net.block_shape
+        room = dict(w=net.i0, e=ni - net.i0 - net.ni, s=net.j0, n=nj - net.j0 - net.nj)
+        return "".join(k for k, v in room.items() if v == 1)
+
+    def _block(self, cur, word):
+        key = (cur, word)
+        b = self._blocks.get(key)
+        if b is None:
+            from . import abi
+            flags = sum(abi.UPSTREAM_FLAG["ring_" + s] for s in self.ring_sides())
+            b = self._blocks[key] = self.engine.flow_upstream_block(self.net.dir, self._sum, self.pend[cur], self.pend[1 - cur], self.jump[cur],
+                                                                    self.jump[1 - cur], self.changed[word:word + 1], flags=flags,
+                                                                    weight=self.weight, inflow=self.inflow)
+        return b
+
+    def _planes(self):
+        torch = self.torch
+        shape, dev = self.net.block_shape, self.net.dir.device
+        i64 = lambda: torch.empty(shape, dtype=torch.int64, device=dev)      # noqa: E731
+        i32 = lambda: torch.empty(shape, dtype=torch.int32, device=dev)      # noqa: E731
+        self._sum, self.pend, self.jump = i64(), [i64(), i64()], [i32(), i32()]
+        self.changed = torch.zeros(self.cap, dtype=torch.int32, device=dev)      # a word per pass
+        sides = self.ring_sides()
+        self.inflow = self._ring = self._feeds = None
+        if sides:
+            ring = np.zeros(shape, bool)
+            for s, sl in (("w", np.s_[:, 0]), ("e", np.s_[:, -1]), ("s", np.s_[0, :]), ("n", np.s_[-1, :])):
+                if s in sides:
+                    ring[sl] = True
+            self._ring = torch.from_numpy(ring).to(dev)
+            self.inflow = torch.zeros(shape, dtype=torch.int64, device=dev)
+        self._blocks = {}
+
+    def begin(self):
+        """The planes (made once, kept with the inflow they hold) and noahmp_hip_flow_upstream_init: one launch."""
+        torch = self.torch
+        if self._sum is None or tuple(self._sum.shape) != self.net.block_shape:
+            self._planes()
+        self.cur = self.passes = 0
+        self.converged = False
+        torch.cuda.current_stream().synchronize()
+        self.engine.flow_upstream_init(self._block(0, 0))
+        self.engine.stream_sync()
+        if self._ring is not None and self._feeds is None:               # the ring cells that push into the tile: a function of dir alone
+            self._feeds = self._ring & (self.jump[0] >= 0)
+
+    def accumulate(self, check=UPSTREAM_CHECK):
+        """noahmp_hip_flow_upstream_pass until a pass pushes nothing or the cap of ceil(log2(ni*nj)) + 1 passes: `check` passes are
+        enqueued in a row, each with a flag word of its own, and the host waits once per batch.  self.passes: the passes up to and
+        including the first in which nobody pushed (a batch may have made up to check - 1 more: they change no word of sum).  Returns
+        self.converged: True, or False at the cap -- caller-given directions hold a cycle."""
+        torch = self.torch
+        self.changed.zero_()
+        torch.cuda.current_stream().synchronize()
+        done = 0
+        while done < self.cap:
+            n = min(int(check), self.cap - done)
+            for k in range(done, done + n):
+                self.engine.flow_upstream_pass(self._block(self.cur, k))
+                self.cur = 1 - self.cur
+            self.engine.stream_sync()
+            flags = self.changed[done:done + n].cpu().numpy()
+            done += n
+            still = np.nonzero(flags == 0)[0]
+            if still.size:
+                self.passes = done - n + int(still[0]) + 1
+                self.converged = True
+                return True
+        self.passes = done
+        self.converged = False
+        return False
+
+    def halo_planes(self):
+        """sum as two float32 views of int32 planes, the low and the high words: what travels in a ring exchange (every mover copies
+        words).  The same two planes every time."""
+        torch = self.torch
+        words = self._sum.view(torch.int32).view(self._sum.shape + (2,))
+        if self._halo is None:
+            self._halo = [torch.empty(self._sum.shape, dtype=torch.int32, device=self._sum.device) for _ in range(2)]
+        for k in range(2):
+            self._halo[k].copy_(words[..., k])
+        return [h.view(torch.float32) for h in self._halo]
+
+    def absorb_ring(self):
+        """After the exchange of halo_planes(): the ring cells' words become inflow.  Returns True when a ring cell that pushes into the
+        tile holds another word than before (the others change nothing here)."""
+        torch = self.torch
+        got = torch.stack(self._halo, dim=-1).contiguous().view(torch.int64)[..., 0]
+        new = torch.where(self._ring, got, torch.zeros_like(got))
+        moved = bool(((new != self.inflow) & self._feeds).any().item())
+        self.inflow.copy_(new)
+        return moved
+
+    def run(self, comm=None, geom=None, strict=True, check=UPSTREAM_CHECK, max_rounds=None):
+        """init and the passes; returns sum.  With a comm (the block's ring sides are owned by neighbour ranks) ROUNDS: round 0 with
+        inflow = 0, then { comm.exchange_halo of the low and the high words of sum; inflow = the ring; init and the passes again where the
+        ring changed; comm.agree_any(ring changed) } until no rank's ring changed.  The ring values only grow; a flow path that changes
+        its owner k times is summed after round k, so the loop makes at most (the largest k) + 2 rounds, the last of which only finds the
+        rings unchanged.  A cycle ACROSS ranks grows for ever: max_rounds (the same on every rank; None = no limit) raises when reached --
+        Basins.run marks such cells PENDING beforehand.
+        THE STREAM RULE of FlowNetwork.step holds: the exchange runs on torch's current stream, the launches on the engine's; each waits
+        for the other.
+        strict: passes that still push at the cap (a cycle of the directions inside the block) raise RuntimeError; strict=False leaves
+        converged = False and the sums as they are."""
+        torch = self.torch
+        if self.ring_sides() and comm is None:
+            raise ValueError("a block with a ring needs the comm that fills it")
+        if self.inflow is not None:
+            self.inflow.zero_()
+        self.begin()
+        ok = self.accumulate(check)
+        self.rounds = 1
+        while comm is not None:
+            if max_rounds is not None and self.rounds >= int(max_rounds):
+                raise RuntimeError("Upstream.run: the ring still changes on some rank after %d rounds: a cycle across ranks?" % self.rounds)
+            self.engine.stream_sync()                                    # sum is written before it travels
+            planes = self.halo_planes()
+            comm.exchange_halo(planes, geom)
+            torch.cuda.current_stream().synchronize()                    # ... and its ring has arrived before init reads it
+            moved = self.absorb_ring()
+            if moved:
+                self.begin()
+                ok = self.accumulate(check) and ok
+            self.rounds += 1
+            if not comm.agree_any(moved):
+                break
+        if self.inflow is not None:                                      # ring cells show their owner's latest word
+            self._sum.copy_(torch.where(self._ring, self.inflow, self._sum))
+            torch.cuda.current_stream().synchronize()
+        self.converged = ok
+        if strict and not ok:
+            raise RuntimeError("Upstream.run: cells still push after the cap of %d passes: the directions hold a cycle (strict=False keeps "
+                               "the sums; Basins marks the cells)" % self.cap)
+        return self._sum
+
+    # ---- what comes out
+    @property
+    def sum(self):
+        """int64 block plane of uint64 words: the sum over every cell's upstream area, itself included; ring cells hold their inflow."""
+        return self._sum
+
+    def cells(self, **kw):
+        """run() with unit weights: the number of cells that drain through every cell (FlowNetwork.upstream_cells in 64 bits)."""
+        self.set_weight(None)
+        return self.run(**kw)
+
+    def channel_mask(self, threshold):
+        """bool block plane: sum >= threshold (a channel begins where enough area drains through a cell)."""
+        return self._sum >= int(threshold)
+
+    @staticmethod
+    def mean_of(field_sum, weight_sum):
+        """The upstream mean of a field: the sums of Upstream runs with weights quantise(field * w, .) and quantise(w, .), divided in
+        float64 (times the ratio of the two steps, which is the caller's); NaN where weight_sum is 0."""
+        import torch
+        f, w = field_sum.to(torch.float64), weight_sum.to(torch.float64)
+        return f / w.masked_fill(w == 0, float("nan"))
