@@ -975,6 +975,57 @@ class Engine:
         passes.  One kernel launch, enqueued only (noahmp_hip_flow_upstream_pass)."""
         self._call("noahmp_hip_flow_upstream_pass", C.byref(block), stream)
 
+    # ---- kinematic-wave routing with Manning friction on the D8 network (noahmp_channel.hip; helper: noahmp_amd/routing.py ChannelFlow)
+    @staticmethod
+    def flow_channel_block(dir, manning, length, conv, dx, dy, smin, height=None, slope=None):
+        """A noahmp_flow_channel block over the (nj, ni) WINDOW plane dir (uint8, device): manning, length, conv and exactly one of
+        height and slope are float32 planes of the same shape.  The tensors are kept alive by the returned block."""
+        import torch
+        assert dir.dim() == 2 and dir.is_contiguous() and dir.dtype == torch.uint8
+        keep = dict(height=height, slope=slope, dir=dir, manning=manning, length=length, conv=conv)
+        for name, t in keep.items():
+            if t is not None and name != "dir":
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == dir.numel(), name
+        b = abi.FlowChannel()
+        _fill(b, keep)
+        b.nj, b.ni = (int(v) for v in dir.shape)
+        b.dx, b.dy, b.smin = float(dx), float(dy), float(smin)
+        return b
+
+    def flow_channel(self, block, stream=None):
+        """The flow length along its direction and conv = sqrt(max(s, smin)) / n of every cell of a block of Engine.flow_channel_block.
+        One kernel launch, enqueued only, once per terrain (noahmp_hip_flow_channel)."""
+        self._call("noahmp_hip_flow_channel", C.byref(block), stream)
+
+    @staticmethod
+    def route_kinematic_block(inmask, col_index, area, width, length, conv, storage, out_old, out_new, runoff_a, runoff_b, scale, dt,
+                              depth=None, diag=None):
+        """A noahmp_route_kinematic block over the (nj, ni) WINDOW: inmask uint8, col_index int32, the others float32 device planes of
+        the window; runoff_a / runoff_b (or None) in the column order of the store; depth a float32 plane or None; diag an int32 tensor
+        of two words or None.  The tensors are kept alive by the returned block."""
+        import torch
+        assert inmask.dim() == 2 and inmask.dtype == torch.uint8 and col_index.dtype == torch.int32
+        keep = dict(inmask=inmask, col_index=col_index, area=area, width=width, length=length, conv=conv, storage=storage, out_old=out_old,
+                    out_new=out_new, runoff_a=runoff_a, runoff_b=runoff_b, depth=depth)
+        for name, t in keep.items():
+            if t is not None:
+                assert t.is_contiguous() and (name.startswith("runoff") or t.numel() == inmask.numel()), name
+                assert name in ("inmask", "col_index") or t.dtype == torch.float32, name
+        if diag is not None:
+            assert diag.dtype == torch.int32 and diag.is_contiguous() and diag.numel() >= 2
+            keep["diag"] = diag
+        b = abi.RouteKinematic()
+        _fill(b, keep)
+        b.nj, b.ni = (int(v) for v in inmask.shape)
+        b.scale, b.dt = float(scale), float(dt)
+        return b
+
+    def route_kinematic(self, block, ncol, stream=None):
+        """One kinematic-wave step of a block of Engine.route_kinematic_block: every owned cell gathers what its upstream neighbours
+        released in the call before, adds its column's runoff and releases Manning's discharge of what it holds, at most all of it.
+        One kernel launch, enqueued only (noahmp_hip_route_kinematic)."""
+        self._call("noahmp_hip_route_kinematic", C.byref(block), int(ncol), stream)
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

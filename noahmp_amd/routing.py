@@ -1,7 +1,8 @@
 """Discharge of a device-resident run: cell-to-cell linear reservoirs on a D8 network (noahmp_hip_flow_terrain / _flow_inmask /
 _flow_accumulate / noahmp_hip_route_runoff), on raw terrain or on terrain conditioned on the device (noahmp_hip_flow_fill_init /
 noahmp_hip_flow_fill), the basins of gauge cells on that network (noahmp_hip_flow_basin_init / _jump / _resolve; class Basins below)
-and the weighted upstream sums (noahmp_hip_flow_upstream_init / _pass; class Upstream below).
+and the weighted upstream sums (noahmp_hip_flow_upstream_init / _pass; class Upstream below), and a kinematic wave with Manning
+friction in place of the linear reservoirs (noahmp_hip_flow_channel / noahmp_hip_route_kinematic; class ChannelFlow below).
 
     net = FlowNetwork(engine, ni, nj)                              # the tile of the store
     net.set_terrain(height, dx, dy, origin=(i0, j0))               # once: height is a WINDOW = tile + 2 cells where there is a neighbour
@@ -16,8 +17,8 @@ and the weighted upstream sums (noahmp_hip_flow_upstream_init / _pass; class Ups
 Every cell gathers what its upstream neighbours released in the call before, adds (RUNSFXY + RUNSBXY) * dt * 1e-3 * area of its column
 and releases the fraction `release` of its storage; water leaves the network at the cells without a direction (outlets, pits, the coast).
 The window planes (the BLOCK: the tile plus a 1-cell ring where the window given has room for one) never move; a sorted store is followed
-through col_index alone.  Not represented: kinematic or diffusive wave, channel geometry, backwater, losses and lakes, a celerity above
-one cell per call (nsub sub-steps).
+through col_index alone.  Not represented by the reservoirs: a celerity that depends on the water held (ChannelFlow does that), a
+celerity above one cell per call (nsub sub-steps); by neither: diffusive wave, backwater, losses and lakes.
 
 Conditioning a raw DEM (DepressionFill; set_terrain(fill=eps); set_terrain_filled): the surface W* of priority-flood + epsilon, made on the
 device as the fixed point of a monotone relaxation, the same bits in every schedule and every decomposition.  Built: every cell that can
@@ -164,6 +165,7 @@ class FlowNetwork:
         self._area_default = True                                        # area is dx*dy of the last set_directions, not the caller's
         self.filled = None                                               # the filled height plane of set_terrain(fill=...) / set_terrain_filled
         self.fill_calls = 0                                              # calls of noahmp_hip_flow_fill it took
+        self.window_shape = self.window_block = None                     # the window of the last set_directions and the block's slices in it
 
     # ---- the network
     @staticmethod
@@ -250,6 +252,7 @@ class FlowNetwork:
         if int(dir_window.max().item()) > 8:
             raise ValueError("directions are 0 (none) or 1..8 (E, NE, N, NW, W, SW, S, SE); FlowNetwork.from_esri converts ESRI codes")
         block, (self.i0, self.j0) = self._block_of(tuple(dir_window.shape), origin)
+        self.window_shape, self.window_block = tuple(dir_window.shape), block      # for ChannelFlow: cutting a plane of the same window
         self.dir = dir_window[block].contiguous()
         self.inmask = torch.empty_like(self.dir)
         self.dx, self.dy = (float(dx), float(dy)) if dx is not None and dy is not None else (None, None)
@@ -373,6 +376,17 @@ class FlowNetwork:
         copies are done), which is in general not the stream the launch runs on.  So after every launch step() waits for `stream`, runs
         the exchange, and waits for torch's current stream: the next launch -- the next sub-step, or the next step's -- reads a ring that
         has arrived, whatever the two streams are."""
+        ra, rb = self._runoff_planes(store, fields, nsub)
+        scale = float(np.float32(dt) * np.float32(1e-3)) / nsub
+
+        def launch(out_old, out_new):
+            b = self.engine.route_block(self.inmask, self.col_index, self.area, self.release, self.storage, out_old, out_new, ra, rb, scale)
+            self.engine.route_runoff(b, self.ncell, stream=stream)
+
+        self._sub_steps(launch, dt, nsub, comm, geom, stream)
+
+    def _runoff_planes(self, store, fields, nsub):
+        """What every per-step call checks first; returns the one or two runoff planes of the store."""
         if self.dir is None:
             raise ValueError("call set_terrain() or set_directions() first")
         if self.area is None:
@@ -380,14 +394,14 @@ class FlowNetwork:
         assert store.ni == self.ni and store.nj == self.nj and 1 <= len(fields) <= 2 and nsub >= 1
         if not self._input_known:
             self._auto_input(store)                                      # once: the columns the step advances
-        ra = store.a[fields[0]]
-        rb = store.a[fields[1]] if len(fields) > 1 else None
-        scale = float(np.float32(dt) * np.float32(1e-3)) / nsub
+        return store.a[fields[0]], (store.a[fields[1]] if len(fields) > 1 else None)
+
+    def _sub_steps(self, launch, dt, nsub, comm, geom, stream):
+        """The loop of step() and ChannelFlow.step(): nsub times launch(out_old, out_new), ping-ponging the two out planes, with the
+        exchange of the new plane under THE STREAM RULE of step()."""
         for _ in range(int(nsub)):
             new = 1 - self.cur
-            b = self.engine.route_block(self.inmask, self.col_index, self.area, self.release, self.storage, self.out[self.cur], self.out[new],
-                                        ra, rb, scale)
-            self.engine.route_runoff(b, self.ncell, stream=stream)
+            launch(self.out[self.cur], self.out[new])
             self.cur = new
             if comm is not None:
                 self.engine.stream_sync(stream)                          # out[new] is written before it travels
@@ -886,3 +900,156 @@ class Upstream:
         import torch
         f, w = field_sum.to(torch.float64), weight_sum.to(torch.float64)
         return f / w.masked_fill(w == 0, float("nan"))
+
+
+class ChannelFlow:
+    """Kinematic-wave routing with Manning friction on a FlowNetwork (noahmp_hip_flow_channel / noahmp_hip_route_kinematic): where
+    FlowNetwork.step releases a constant fraction, a cell releases Manning's discharge of a rectangular section whose depth follows from
+    what the cell holds, at most all of it.
+
+        ch = ChannelFlow(net)                                    # a FlowNetwork with directions set; works on net.storage, net.out, net.cur
+        area = up.sum.double() * step                            # Upstream: the contributing area [m2]
+        w = ChannelFlow.width_from_area(area, 2.0, 0.4, 5e6, net.dir, dx, dy)
+        ch.set_geometry(w, 0.05)                                 # once: bed slopes from net.filled, one launch
+        engine.noahmplsm(store, ...); ch.step(store, dt, nsub=2) # per step, INSTEAD of net.step
+        ch.courant(), ch.capped(); ch.reset_diag()               # 5/3 * the largest vel*dt/length since the reset; keep it near or below 1
+        net.discharge(), net.state_dict(), Regions / probes over net.out: as with net.step
+
+    Not represented: diffusive wave and backwater, trapezoidal sections, losses, lakes with storage, an implicit solve; nsub is the
+    caller's choice, read from courant()."""
+
+    def __init__(self, net):
+        if net.dir is None:
+            raise ValueError("the FlowNetwork has no directions: call set_terrain() or set_directions() first")
+        self.net, self.engine, self.torch = net, net.engine, net.torch
+        self.width = self.manning = self.length = self.conv = None
+        self.smin = None
+        self._depth = None
+        self.diag = None                                                 # two device words: the bits of the largest cr, the capped cells
+
+    def _plane(self, plane, name, ring):
+        """A number, a plane of the block or a plane of the tile (its ring cells, which no call computes, get `ring`)."""
+        torch, net = self.torch, self.net
+        dev = net.dir.device
+        if not torch.is_tensor(plane):
+            return torch.full(net.block_shape, float(plane), dtype=torch.float32, device=dev)
+        plane = plane.to(torch.float32)
+        if tuple(plane.shape) == (net.nj, net.ni) and net.block_shape != (net.nj, net.ni):
+            full = torch.full(net.block_shape, float(ring), dtype=torch.float32, device=dev)
+            net.tile_view(full).copy_(plane)
+            plane = full
+        assert tuple(plane.shape) == net.block_shape, "%s: a number, a plane of the block %s or of the tile" % (name, net.block_shape)
+        return plane.contiguous()
+
+    def _cut(self, plane, name):
+        """A plane of the block as it is; a plane of the window given to set_terrain / set_directions (same origin) cut to the block."""
+        net = self.net
+        plane = plane.to(self.torch.float32)
+        if tuple(plane.shape) == net.block_shape:
+            return plane.contiguous()
+        if net.window_shape is not None and tuple(plane.shape) == net.window_shape:
+            return plane[net.window_block].contiguous()
+        raise ValueError("%s: a plane of the block %s or of the window %s" % (name, net.block_shape, net.window_shape))
+
+    def set_geometry(self, width, manning, smin=1e-4, height=None, slope=None):
+        """width [m] and manning [s m^-1/3]: numbers, or float32 device planes of the block or the tile.  The bed slope comes from
+        `slope` (a plane), else from `height`, else from net.filled: the drop to the downstream cell over the distance, at least smin.
+        A height or slope plane is one of the block, or one of the window given to set_terrain with the same origin.  One launch; length
+        and conv are kept.  A cell with manning not > 0 holds its water."""
+        torch, net = self.torch, self.net
+        if net.dx is None:
+            raise ValueError("set_geometry needs the dx, dy of set_terrain / set_directions")
+        if slope is None and height is None:
+            height = net.filled
+        if slope is None and height is None:
+            raise ValueError("no bed slope: the network has no filled surface (set_terrain(fill=...) / set_terrain_filled); give height= or slope=")
+        self.width = self._plane(width, "width", 1.0)
+        assert bool((self.width > 0).all().item()), "width must be > 0 everywhere"
+        self.manning = self._plane(manning, "manning", 0.0)
+        h = s = None
+        if slope is not None:
+            s = self._cut(slope, "slope")
+        else:
+            h = self._cut(height, "height")
+        dev = net.dir.device
+        self.length = torch.empty(net.block_shape, dtype=torch.float32, device=dev)
+        self.conv = torch.empty(net.block_shape, dtype=torch.float32, device=dev)
+        self._depth = torch.zeros(net.block_shape, dtype=torch.float32, device=dev)
+        self.diag = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.smin = float(smin)
+        torch.cuda.current_stream().synchronize()
+        self.engine.flow_channel(self.engine.flow_channel_block(net.dir, self.manning, self.length, self.conv, net.dx, net.dy, self.smin,
+                                                                height=h, slope=s))
+        self.engine.stream_sync()
+
+    @staticmethod
+    def width_from_area(area_m2, a, b, threshold_m2, dir, dx, dy):
+        """The width of every cell's rectangular section [m], float32, numpy in numpy out, tensor in tensor out.  Where area_m2 >=
+        threshold_m2 (a channel cell) the hydraulic-geometry width a * area^b, made in float64 on the host and rounded once; elsewhere
+        (a hillslope cell: sheet flow) the cell's width ACROSS its direction: dy for E / W, dx for N / S, dx*dy/diagonal for the diagonals,
+        dx where there is no direction.  area_m2: Upstream.sum() times the quantisation step.  dir: the directions of the same cells."""
+        is_np = isinstance(area_m2, np.ndarray)
+        area = np.asarray(area_m2 if is_np else area_m2.cpu().numpy(), np.float64)
+        d = np.asarray(dir if isinstance(dir, np.ndarray) else dir.cpu().numpy())
+        assert d.shape == area.shape
+        dx, dy = float(dx), float(dy)
+        diag = math.sqrt(dx * dx + dy * dy)
+        across = np.where((d == 0) | (d > 8), dx, np.where(d % 2 == 0, dx * dy / diag, np.where((d == 3) | (d == 7), dx, dy)))
+        with np.errstate(all="ignore"):
+            w = np.where(area >= float(threshold_m2), float(a) * np.power(area, float(b)), across).astype(np.float32)
+        if is_np:
+            return w
+        import torch
+        return torch.from_numpy(w).to(area_m2.device)
+
+    def step(self, store, dt, fields=("runsfxy", "runsbxy"), nsub=1, comm=None, geom=None, stream=None):
+        """One model step of routing after Engine.noahmplsm, INSTEAD of FlowNetwork.step: nsub launches with dt/nsub and scale =
+        dt*1e-3/nsub on the network's storage and out planes; the stream rule and the exchange of out are those of FlowNetwork.step.
+        depth and the two diag words are written by every launch; diag accumulates until reset_diag()."""
+        net = self.net
+        if self.conv is None:
+            raise ValueError("call set_geometry() first")
+        ra, rb = net._runoff_planes(store, fields, nsub)
+        scale = float(np.float32(dt) * np.float32(1e-3)) / nsub
+        dts = float(dt) / nsub
+
+        def launch(out_old, out_new):
+            b = self.engine.route_kinematic_block(net.inmask, net.col_index, net.area, self.width, self.length, self.conv, net.storage,
+                                                  out_old, out_new, ra, rb, scale, dts, depth=self._depth, diag=self.diag)
+            self.engine.route_kinematic(b, net.ncell, stream=stream)
+
+        net._sub_steps(launch, dt, nsub, comm, geom, stream)
+
+    def follow(self, store):
+        """After Engine.sort_store(store): FlowNetwork.follow -- only col_index is rewritten."""
+        self.net.follow(store)
+
+    def depth(self):
+        """The water depth h [m] of the last launch, a plane of the block (0 where a cell held no water or has no conveyance)."""
+        return self._depth
+
+    def reset_diag(self):
+        """Zero the two diag words (the calls never do)."""
+        self.torch.cuda.current_stream().synchronize()
+        self.engine.stream_sync()
+        self.diag.zero_()
+        self.torch.cuda.current_stream().synchronize()
+
+    def _diag_words(self):
+        self.engine.stream_sync()                                        # the one host wait
+        w = self.diag.cpu().numpy().view(np.uint32)
+        return int(w[0]), int(w[1])
+
+    def courant(self, comm=None):
+        """5/3 * the largest vel*dt/length of any owned cell in any launch since reset_diag(): the Courant number of the kinematic
+        celerity on a wide section.  NaN when a cell's was NaN.  With a comm the maximum over the ranks.  One host wait."""
+        bits = self._diag_words()[0]
+        if comm is not None:
+            bits = int(comm.reduce_max(bits))                            # uint32 bits are exact in float64 and monotone like the floats
+        return 5.0 / 3.0 * float(np.array([bits], np.uint32).view(np.float32)[0])
+
+    def capped(self, comm=None):
+        """The number of (cell, launch) pairs since reset_diag() in which a cell released all it held (mod 2^32 per rank); with a comm
+        the sum over the ranks.  One host wait."""
+        n = self._diag_words()[1]
+        return int(comm.reduce_sum(n)) if comm is not None else n
