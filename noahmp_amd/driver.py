@@ -1026,6 +1026,56 @@ class Engine:
         One kernel launch, enqueued only (noahmp_hip_route_kinematic)."""
         self._call("noahmp_hip_route_kinematic", C.byref(block), int(ncol), stream)
 
+    # ---- lakes on the D8 network: level-pool storage and outflow (noahmp_lakes.hip; helper: noahmp_amd/routing.py Lakes)
+    @staticmethod
+    def lake_take_block(member_cell, member_lake, storage, inflow, quantum):
+        """A noahmp_lake_take block: member_cell and member_lake int32 device lists of one length (-1: a pad), storage the float32 window
+        plane of the routing call, inflow an int64 device tensor of one word per lake.  The tensors are kept alive by the returned block."""
+        import torch
+        assert member_cell.dtype == torch.int32 and member_lake.dtype == torch.int32 and member_cell.numel() == member_lake.numel()
+        assert storage.dtype == torch.float32 and inflow.dtype == torch.int64
+        keep = dict(member_cell=member_cell, member_lake=member_lake, storage=storage, inflow=inflow)
+        for name, t in keep.items():
+            assert t.is_contiguous(), name
+        b = abi.LakeTake()
+        _fill(b, keep)
+        b.nmember, b.nlake, b.ncell, b.quantum = int(member_cell.numel()), int(inflow.numel()), int(storage.numel()), float(quantum)
+        return b
+
+    def lake_take(self, block, stream=None):
+        """The whole quanta of every listed member's storage leave the cell and are added to its lake's inflow word, an integer sum.
+        One kernel launch, enqueued only (noahmp_hip_lake_take)."""
+        self._call("noahmp_hip_lake_take", C.byref(block), stream)
+
+    @staticmethod
+    def lake_release_block(volume, inflow, params, outlet_cell, out_new, quantum, dt, level=None, outflow=None, diag=None):
+        """A noahmp_lake_release block: volume and inflow int64 device words per lake, params a dict of the seven float64 device planes
+        (area, weir_h, weir_c, weir_l, orifice_h, orifice_c, orifice_a), outlet_cell int32 per lake, out_new the float32 window plane of
+        the routing call; level (float64), outflow (float32) per lake and diag (one int32 word) or None.  The tensors are kept alive by
+        the returned block."""
+        import torch
+        nlake = int(volume.numel())
+        assert volume.dtype == torch.int64 and inflow.dtype == torch.int64 and inflow.numel() == nlake
+        assert outlet_cell.dtype == torch.int32 and outlet_cell.numel() == nlake and out_new.dtype == torch.float32
+        keep = dict(volume=volume, inflow=inflow, outlet_cell=outlet_cell, out_new=out_new, level=level, outflow=outflow, diag=diag)
+        for name in ("area", "weir_h", "weir_c", "weir_l", "orifice_h", "orifice_c", "orifice_a"):
+            t = keep[name] = params[name]
+            assert t.dtype == torch.float64 and t.numel() == nlake, name
+        assert level is None or (level.dtype == torch.float64 and level.numel() == nlake)
+        assert outflow is None or (outflow.dtype == torch.float32 and outflow.numel() == nlake)
+        assert diag is None or (diag.dtype == torch.int32 and diag.numel() >= 1)
+        for name, t in keep.items():
+            assert t is None or t.is_contiguous(), name
+        b = abi.LakeRelease()
+        _fill(b, keep)
+        b.nlake, b.ncell, b.quantum, b.dt = nlake, int(out_new.numel()), float(quantum), float(dt)
+        return b
+
+    def lake_release(self, block, stream=None):
+        """volume += inflow, inflow = 0, the level-pool outflow of every lake (weir + orifice, at most what it holds) leaves volume and is
+        written to out_new at the outlet.  One kernel launch, enqueued only (noahmp_hip_lake_release)."""
+        self._call("noahmp_hip_lake_release", C.byref(block), stream)
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

@@ -376,6 +376,18 @@ class Comm:
         self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
         return float(t.item())
 
+    def reduce_sum_words(self, words):
+        """The sum over the ranks of an int64 tensor of words (routing.Lakes: the lakes' inflow), written back in place and returned: an
+        integer sum, exact and independent of order.  Without dist the tensor as it is.  The caller has waited for the stream that wrote it."""
+        if not self.dist:
+            return words
+        import torch
+        assert words.dtype == torch.int64
+        t = words.detach().to("cpu", copy=True)
+        self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
+        words.copy_(t)
+        return words
+
     def gather_to_root(self, array):
         """numpy array -> list of arrays on rank 0 (None elsewhere); test helper for tile reassembly."""
         if not self.dist:

@@ -18,12 +18,12 @@ Every cell gathers what its upstream neighbours released in the call before, add
 and releases the fraction `release` of its storage; water leaves the network at the cells without a direction (outlets, pits, the coast).
 The window planes (the BLOCK: the tile plus a 1-cell ring where the window given has room for one) never move; a sorted store is followed
 through col_index alone.  Not represented by the reservoirs: a celerity that depends on the water held (ChannelFlow does that), a
-celerity above one cell per call (nsub sub-steps); by neither: diffusive wave, backwater, losses and lakes.
+celerity above one cell per call (nsub sub-steps); by neither: diffusive wave, backwater and losses.  Lakes with storage: class Lakes below.
 
 Conditioning a raw DEM (DepressionFill; set_terrain(fill=eps); set_terrain_filled): the surface W* of priority-flood + epsilon, made on the
 device as the fixed point of a monotone relaxation, the same bits in every schedule and every decomposition.  Built: every cell that can
 reach an outlet drains; flats and filled depressions become ramps of one lift (eps, or one float32 step where eps is below it) per cell
-away from their outlet.  Not built: carving / breaching, lakes with storage, a combined-gradient flat resolution (Garbrecht-Martz).
+away from their outlet.  Not built: carving / breaching, a combined-gradient flat resolution (Garbrecht-Martz).
 Without fill, set_terrain takes the terrain as it is: water leaves the network at every pit.  The contract -- every rounding -- is the
 text in include/noahmp_hip.h.
 """
@@ -166,6 +166,8 @@ class FlowNetwork:
         self.filled = None                                               # the filled height plane of set_terrain(fill=...) / set_terrain_filled
         self.fill_calls = 0                                              # calls of noahmp_hip_flow_fill it took
         self.window_shape = self.window_block = None                     # the window of the last set_directions and the block's slices in it
+        self.after_launch = []                                           # f(out_new, dt_sub, comm, stream) after every launch of a step (Lakes.attach)
+        self.held = None                                                 # bool plane of the block: cells that hold their water (Lakes.set_lakes)
 
     # ---- the network
     @staticmethod
@@ -356,6 +358,7 @@ class FlowNetwork:
     def set_release(self, plane):
         """The fraction of its storage every cell releases per call, in [0, 1] (not checked; 0 holds the water)."""
         self.release = self._plane(plane, "release")
+        self._hold()
 
     def set_velocity(self, velocity, dt):
         """release = 1 - exp(-dt*velocity/length), made in float64 on the host and rounded once; length = dx, dy or the diagonal by the
@@ -367,6 +370,13 @@ class FlowNetwork:
         length = np.where(d == 0, self.dx, np.where(d % 2 == 0, diag, np.where((d == 3) | (d == 7), self.dy, self.dx)))
         r = (1.0 - np.exp(-float(dt) * v / length)).astype(np.float32)
         self.release = self.torch.from_numpy(r).to(self.dir.device).contiguous()
+        self._hold()
+
+    def _hold(self):
+        """release = 0 at the held cells (the members of Lakes.set_lakes), whatever the caller's plane says there."""
+        if self.held is not None and self.release is not None and self.release.shape == self.held.shape:
+            self.release.masked_fill_(self.held, 0.0)
+            self.torch.cuda.current_stream().synchronize()
 
     def step(self, store, dt, fields=("runsfxy", "runsbxy"), nsub=1, comm=None, geom=None, stream=None):
         """One model step of routing after Engine.noahmplsm: nsub launches with scale = dt*1e-3/nsub, ping-ponging the two out planes;
@@ -403,6 +413,8 @@ class FlowNetwork:
             new = 1 - self.cur
             launch(self.out[self.cur], self.out[new])
             self.cur = new
+            for f in self.after_launch:                                  # e.g. the lakes: take and release, before out[new] travels
+                f(self.out[new], float(dt) / nsub, comm, stream)
             if comm is not None:
                 self.engine.stream_sync(stream)                          # out[new] is written before it travels
                 comm.exchange_halo([self.out[new]], geom)
@@ -915,7 +927,7 @@ class ChannelFlow:
         ch.courant(), ch.capped(); ch.reset_diag()               # 5/3 * the largest vel*dt/length since the reset; keep it near or below 1
         net.discharge(), net.state_dict(), Regions / probes over net.out: as with net.step
 
-    Not represented: diffusive wave and backwater, trapezoidal sections, losses, lakes with storage, an implicit solve; nsub is the
+    Not represented: diffusive wave and backwater, trapezoidal sections, losses, an implicit solve (lakes: class Lakes); nsub is the
     caller's choice, read from courant()."""
 
     def __init__(self, net):
@@ -981,6 +993,9 @@ class ChannelFlow:
         self.engine.flow_channel(self.engine.flow_channel_block(net.dir, self.manning, self.length, self.conv, net.dx, net.dy, self.smin,
                                                                 height=h, slope=s))
         self.engine.stream_sync()
+        if net.held is not None:                                         # the members of Lakes.set_lakes hold their water
+            self.conv.masked_fill_(net.held, 0.0)
+            torch.cuda.current_stream().synchronize()
 
     @staticmethod
     def width_from_area(area_m2, a, b, threshold_m2, dir, dx, dy):
@@ -1053,3 +1068,231 @@ class ChannelFlow:
         the sum over the ranks.  One host wait."""
         n = self._diag_words()[1]
         return int(comm.reduce_sum(n)) if comm is not None else n
+
+
+LAKE_PARAMS = ("area", "weir_h", "weir_c", "weir_l", "orifice_h", "orifice_c", "orifice_a")
+LAKE_WAVE = 64                                                           # every lake's entries are padded to whole waves
+
+
+class Lakes:
+    """Lakes on a FlowNetwork or a ChannelFlow: level-pool storage and outflow (noahmp_hip_lake_take / noahmp_hip_lake_release).
+
+        lakes = Lakes(ch)                                        # or Lakes(net); quantum = 2**-10 m3
+        lake_id, outlet_ij, area = Lakes.from_fill(raw, filled, upstream_sum, 0.5, cell_area=dx * dy)      # once, host, global planes
+        lakes.set_lakes(lake_id_tile, params, outlet_ij, tile_origin=(i0, j0))
+        lakes.attach()                                           # after every launch of net.step / ch.step: take, (sum over ranks,) release
+        ch.step(store, dt, nsub=2)
+        lakes.level(), lakes.outflow(), lakes.volume_m3(), lakes.emptied()
+
+    The members of a lake hold everything that reaches them (release and conv are zeroed there, also when set_release, set_velocity or
+    set_geometry is called later); after each launch the whole quanta of their storage move to the lake's volume word and the level-pool
+    outflow of a weir and an orifice is written to out at the outlet, where the next launch's gather picks it up.  Water is conserved
+    exactly.  Not built: evaporation and precipitation on the lake surface, hypsometric (level-dependent) area, an implicit or
+    Runge-Kutta level-pool solve, reservoir operating rules, backwater into inflowing channels."""
+
+    def __init__(self, flow, quantum=2.0 ** -10):
+        self.ch = flow if isinstance(flow, ChannelFlow) else None
+        self.net = flow.net if self.ch is not None else flow
+        if self.net.dir is None:
+            raise ValueError("the FlowNetwork has no directions: call set_terrain() or set_directions() first")
+        self.engine, self.torch = self.net.engine, self.net.torch
+        self.quantum = float(quantum)
+        m, e = math.frexp(self.quantum)
+        if m != 0.5 or not -40 <= e - 1 <= 20:
+            raise ValueError("quantum must be an exact power of two in [2^-40, 2^20]")
+        self.nlake = 0
+        self.member_cell = self.member_lake = self.outlet_cell = None
+        self.volume = self.inflow = self.params = None
+        self._level = self._outflow = self.diag = None
+        self._blocks = {}
+
+    # ---- the host helper
+    @staticmethod
+    def from_fill(raw, filled, upstream_sum, min_depth, min_cells=1, cell_area=1.0):
+        """Lakes of a filled terrain, numpy, once per terrain on GLOBAL (nj, ni) planes: the 8-connected components of
+        filled - raw >= min_depth with at least min_cells cells, numbered 1.. by their smallest cell index ascending.  The outlet of a
+        lake is its member with the largest upstream_sum (ties: the smallest cell index); area = cells * cell_area.
+        Returns (lake_id int32 plane, outlet_ij int64 (nlake, 2) of global (i, j), area float64 (nlake,))."""
+        raw, filled, up = np.asarray(raw, np.float64), np.asarray(filled, np.float64), np.asarray(upstream_sum)
+        assert raw.ndim == 2 and raw.shape == filled.shape == up.shape
+        nj, ni = raw.shape
+        with np.errstate(invalid="ignore"):
+            mask = (filled - raw) >= float(min_depth)
+        big = nj * ni
+        cell = np.arange(big, dtype=np.int64).reshape(nj, ni)
+        label = np.where(mask, cell, big)
+        pad = np.full((nj + 2, ni + 2), big, np.int64)
+        while True:                                                      # the smallest cell index of every component: min over the
+            pad[1:-1, 1:-1] = label                                      # neighbours, then pointer jumping through the labels
+            new = label
+            for dj in (0, 1, 2):
+                for di in (0, 1, 2):
+                    new = np.minimum(new, pad[dj:dj + nj, di:di + ni])
+            new = np.where(mask, new, big)
+            flat = np.append(new.ravel(), big)
+            for _ in range(64):
+                nxt = flat[flat]
+                if (nxt == flat).all():
+                    break
+                flat = nxt
+            new = flat[:-1].reshape(nj, ni)
+            if (new == label).all():
+                break
+            label = new
+        roots, inverse, counts = np.unique(label[mask], return_inverse=True, return_counts=True)
+        keep = counts >= int(min_cells)
+        number = np.zeros(roots.size, np.int32)
+        number[keep] = np.arange(1, int(keep.sum()) + 1, dtype=np.int32)
+        lake_id = np.zeros((nj, ni), np.int32)
+        lake_id[mask] = number[inverse]
+        nlake = int(keep.sum())
+        member = lake_id > 0
+        mc, ml = cell[member], lake_id[member].astype(np.int64) - 1
+        mu = up[member].astype(np.int64) if up.dtype.kind in "iu" else up[member].astype(np.float64)
+        order = np.lexsort((-mc, mu, ml))                               # the last entry of every lake: the largest sum, then the smallest cell
+        last = np.r_[np.nonzero(np.diff(ml[order]))[0], order.size - 1] if order.size else np.zeros(0, np.int64)
+        oc = mc[order][last]
+        outlet_ij = np.stack([oc % ni, oc // ni], axis=1).astype(np.int64).reshape(nlake, 2)
+        area = counts[keep].astype(np.float64) * float(cell_area)
+        return lake_id, outlet_ij, area
+
+    # ---- the lakes of this tile
+    def set_lakes(self, lake_id, params, outlet_ij, tile_origin=(0, 0)):
+        """lake_id: int32 plane of the TILE, 0 = none, 1..nlake = global ids, the same on all ranks.  params: a dict of the seven float64
+        arrays of length nlake (LAKE_PARAMS).  outlet_ij: the global (i, j) of every lake's outlet.  tile_origin: the global (i, j) of the
+        tile's cell (0, 0).  Builds the member list of the owned members, sorted by lake, every lake padded to whole waves with -1; the
+        outlet_cell of a lake whose outlet is not on this tile is -1.  Zeroes release (and conv) at the members."""
+        torch, net = self.torch, self.net
+        dev = net.dir.device
+        lid = np.asarray(lake_id.cpu().numpy() if torch.is_tensor(lake_id) else lake_id).astype(np.int64)
+        if lid.shape != (net.nj, net.ni):
+            raise ValueError("lake_id is a plane of the tile (%d, %d)" % (net.nj, net.ni))
+        par = {k: np.ascontiguousarray(params[k], np.float64).ravel() for k in LAKE_PARAMS}
+        nlake = par["area"].size
+        out_ij = np.asarray(outlet_ij, np.int64)
+        if any(v.size != nlake for v in par.values()) or out_ij.size != 2 * nlake or lid.min() < 0 or lid.max() > nlake:
+            raise ValueError("params and outlet_ij have one entry per lake, lake_id holds 0 .. nlake")
+        out_ij = out_ij.reshape(nlake, 2)
+        nj_b, ni_b = net.block_shape
+        d = net.dir.cpu().numpy()
+        from . import abi
+        outlet_cell = np.full(nlake, -1, np.int32)
+        for l in range(nlake):
+            i, j = int(out_ij[l, 0]) - int(tile_origin[0]), int(out_ij[l, 1]) - int(tile_origin[1])
+            if not (0 <= i < net.ni and 0 <= j < net.nj):
+                continue                                                 # another rank owns it
+            if lid[j, i] != l + 1:
+                raise ValueError("the outlet (%d, %d) of lake %d is not a member of it" % (out_ij[l, 0], out_ij[l, 1], l + 1))
+            k = int(d[j + net.j0, i + net.i0])
+            if 1 <= k <= 8:
+                i2, j2 = i + abi.FLOW_DI[k - 1], j + abi.FLOW_DJ[k - 1]
+                if 0 <= i2 < net.ni and 0 <= j2 < net.nj and lid[j2, i2] == l + 1:
+                    raise ValueError("the outlet (%d, %d) of lake %d drains into a member of the same lake" % (out_ij[l, 0], out_ij[l, 1], l + 1))
+            outlet_cell[l] = (j + net.j0) * ni_b + (i + net.i0)
+        jj, ii = np.nonzero(lid > 0)
+        lake = lid[jj, ii] - 1
+        cellb = (jj + net.j0) * ni_b + (ii + net.i0)
+        order = np.lexsort((cellb, lake))
+        lake, cellb = lake[order], cellb[order]
+        counts = np.bincount(lake, minlength=nlake) if lake.size else np.zeros(nlake, np.int64)
+        padded = (counts + LAKE_WAVE - 1) // LAKE_WAVE * LAKE_WAVE
+        start = np.concatenate([[0], np.cumsum(padded)])[:-1] if nlake else np.zeros(0, np.int64)
+        mcell = np.full(int(padded.sum()), -1, np.int32)
+        mlake = np.full(int(padded.sum()), -1, np.int32)
+        if lake.size:
+            first = np.concatenate([[0], np.cumsum(counts)])[:-1]
+            pos = start[lake] + (np.arange(lake.size) - first[lake])
+            mcell[pos], mlake[pos] = cellb, lake
+        held = np.zeros((nj_b, ni_b), bool)
+        held[jj + net.j0, ii + net.i0] = True
+        self.nlake = nlake
+        self.member_cell, self.member_lake = torch.from_numpy(mcell).to(dev), torch.from_numpy(mlake).to(dev)
+        self.outlet_cell = torch.from_numpy(outlet_cell).to(dev)
+        self.params = {k: torch.from_numpy(v.copy()).to(dev) for k, v in par.items()}
+        self.volume = torch.zeros(nlake, dtype=torch.int64, device=dev)
+        self.inflow = torch.zeros(nlake, dtype=torch.int64, device=dev)
+        self._level = torch.zeros(nlake, dtype=torch.float64, device=dev)
+        self._outflow = torch.zeros(nlake, dtype=torch.float32, device=dev)
+        self.diag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._blocks = {}
+        net.held = torch.from_numpy(held).to(dev)
+        net._hold()
+        if self.ch is not None and self.ch.conv is not None:
+            self.ch.conv.masked_fill_(net.held, 0.0)
+        torch.cuda.current_stream().synchronize()
+
+    # ---- the hook
+    def _after_launch(self, out_new, dt_sub, comm, stream):
+        net = self.net
+        if self.nlake == 0:
+            return
+        key = (out_new.data_ptr(), float(dt_sub), net.storage.data_ptr())
+        b = self._blocks.get(key)
+        if b is None:
+            b = self._blocks[key] = (
+                self.engine.lake_take_block(self.member_cell, self.member_lake, net.storage, self.inflow, self.quantum),
+                self.engine.lake_release_block(self.volume, self.inflow, self.params, self.outlet_cell, out_new, self.quantum, dt_sub,
+                                               level=self._level, outflow=self._outflow, diag=self.diag))
+        self.engine.lake_take(b[0], stream=stream)
+        if comm is not None:
+            self.engine.stream_sync(stream)                              # the partial words are written before they are summed
+            words = comm.reduce_sum_words(self.inflow)
+            if words is not self.inflow:
+                self.inflow.copy_(words)
+            self.torch.cuda.current_stream().synchronize()               # ... and the sums have arrived before the release reads them
+        self.engine.lake_release(b[1], stream=stream)
+
+    def attach(self):
+        """Put the hook into net.after_launch: after every launch of FlowNetwork.step / ChannelFlow.step, before out travels."""
+        if self.volume is None:
+            raise ValueError("call set_lakes() first")
+        if self._after_launch not in self.net.after_launch:
+            self.net.after_launch.append(self._after_launch)
+
+    def detach(self):
+        """Take the hook out; the members go on holding what reaches them."""
+        if self._after_launch in self.net.after_launch:
+            self.net.after_launch.remove(self._after_launch)
+
+    # ---- what the lakes hold
+    def _wait(self):
+        self.engine.stream_sync()
+        self.torch.cuda.current_stream().synchronize()
+
+    def level(self):
+        """The level h [m above the datum] every lake's last release was made from (float64 device tensor)."""
+        return self._level
+
+    def outflow(self):
+        """What every lake released in the last call [m3] (float32 device tensor)."""
+        return self._outflow
+
+    def volume_m3(self):
+        """What every lake holds [m3]: words * quantum, float64 numpy.  One host wait."""
+        self._wait()
+        return self.volume.cpu().numpy().astype(np.float64) * self.quantum
+
+    def set_volume_m3(self, v):
+        """volume = floor(v / quantum) words per lake (a number or nlake values)."""
+        self._wait()
+        w = np.floor(np.broadcast_to(np.asarray(v, np.float64), (self.nlake,)) / self.quantum).astype(np.int64)
+        self.volume.copy_(self.torch.from_numpy(w))
+        self.torch.cuda.current_stream().synchronize()
+
+    def emptied(self):
+        """The number of (lake, call) pairs in which a lake released all it held.  One host wait."""
+        self._wait()
+        return int(self.diag.cpu().numpy().view(np.uint32)[0])
+
+    def state_dict(self):
+        """The restart words: volume (int64; with the network's own state_dict the whole restart state)."""
+        self._wait()
+        return dict(volume=self.volume.clone(), quantum=self.quantum)
+
+    def load_state_dict(self, state):
+        if float(state.get("quantum", self.quantum)) != self.quantum:
+            raise ValueError("the restart words were made with another quantum")
+        self._wait()
+        self.volume.copy_(state["volume"])
+        self.inflow.zero_()
+        self.torch.cuda.current_stream().synchronize()
