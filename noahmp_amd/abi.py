@@ -25,6 +25,7 @@ from .abi_spec import FLOW_BASIN_FIELDS, FLOW_BASIN_FLAGS, FLOW_BASIN_LABELS, FL
 from .abi_spec import FLOW_UPSTREAM_FIELDS, FLOW_UPSTREAM_FLAGS
 from .abi_spec import FLOW_CHANNEL_FIELDS, ROUTE_KINEMATIC_FIELDS
 from .abi_spec import LAKE_TAKE_FIELDS, LAKE_RELEASE_FIELDS
+from .abi_spec import FLOW_DROP_FIELDS, ROUTE_DIFFUSIVE_FIELDS, LAKE_DEPTH_FIELDS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libnoahmp_hip.so")
@@ -189,6 +190,21 @@ class LakeTake(C.Structure):
 class LakeRelease(C.Structure):
     """noahmp_lake_release: the words, parameter planes and outputs of noahmp_hip_lake_release."""
     _fields_ = [(n, _hist_ctype(k)) for n, t, k, doc in LAKE_RELEASE_FIELDS]
+
+
+class FlowDrop(C.Structure):
+    """noahmp_flow_drop: the window planes and parameters of noahmp_hip_flow_drop."""
+    _fields_ = [(n, _hist_ctype(k)) for n, t, k, doc in FLOW_DROP_FIELDS]
+
+
+class RouteDiffusive(C.Structure):
+    """noahmp_route_diffusive: the planes and parameters of noahmp_hip_route_diffusive."""
+    _fields_ = [(n, _hist_ctype(k)) for n, t, k, doc in ROUTE_DIFFUSIVE_FIELDS]
+
+
+class LakeDepth(C.Structure):
+    """noahmp_lake_depth: the member list and planes of noahmp_hip_lake_depth."""
+    _fields_ = [(n, _hist_ctype(k)) for n, t, k, doc in LAKE_DEPTH_FIELDS]
 
 
 BASIN_FLAG = {nm.lower(): val for nm, val, doc in FLOW_BASIN_FLAGS}    # "ring_w" .. "ring_n"
@@ -356,6 +372,9 @@ def load_library(path=None):
     lib.noahmp_hip_route_kinematic.argtypes = [C.POINTER(RouteKinematic), C.c_int64, C.c_void_p]
     lib.noahmp_hip_lake_take.argtypes = [C.POINTER(LakeTake), C.c_void_p]
     lib.noahmp_hip_lake_release.argtypes = [C.POINTER(LakeRelease), C.c_void_p]
+    lib.noahmp_hip_flow_drop.argtypes = [C.POINTER(FlowDrop), C.c_void_p]
+    lib.noahmp_hip_route_diffusive.argtypes = [C.POINTER(RouteDiffusive), C.c_int64, C.c_void_p]
+    lib.noahmp_hip_lake_depth.argtypes = [C.POINTER(LakeDepth), C.c_void_p]
     lib.noahmp_hip_scatter_fields.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int),
                                               C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.noahmp_hip_sorted_exchange.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
@@ -411,7 +430,7 @@ def load_library(path=None):
 EXPORTED_SYMBOLS = [
     "noahmp_hip_abi_version", "noahmp_hip_nsoil", "noahmp_hip_sizeof_step_args", "noahmp_hip_sizeof_tables",
     "noahmp_hip_device_count", "noahmp_hip_set_device", "noahmp_hip_set_tables",
-    "noahmp_hip_step", "noahmp_hip_fetch", "noahmp_hip_step_async", "noahmp_hip_sync", "noahmp_hip_sync_timing", "noahmp_hip_sync_step_timing", "noahmp_hip_sync_counts", "noahmp_hip_fetch_cost", "noahmp_hip_init", "noahmp_hip_forcing_prep", "noahmp_hip_forcing_interpolate", "noahmp_hip_forcing_interpolate_prep", "noahmp_hip_declination", "noahmp_hip_gather_fields", "noahmp_hip_output_fields", "noahmp_hip_history_step", "noahmp_hip_history_finish", "noahmp_hip_region_plan_size", "noahmp_hip_region_plan", "noahmp_hip_region_plan_follow", "noahmp_hip_region_scratch_size", "noahmp_hip_region_step", "noahmp_hip_regrid_plan_size", "noahmp_hip_regrid_plan_latlon", "noahmp_hip_forcing_regrid", "noahmp_hip_forcing_regrid_met", "noahmp_hip_regrid_conserve_plan_size", "noahmp_hip_regrid_conserve_plan", "noahmp_hip_regrid_conserve_scratch_size", "noahmp_hip_forcing_regrid_conserve", "noahmp_hip_forcing_cosz_mean", "noahmp_hip_forcing_shortwave", "noahmp_hip_forcing_shadow", "noahmp_hip_forcing_shortwave_lit", "noahmp_hip_skyview", "noahmp_hip_forcing_radiation_sky", "noahmp_hip_wind_terrain", "noahmp_hip_forcing_wind", "noahmp_hip_flow_terrain", "noahmp_hip_flow_inmask", "noahmp_hip_flow_accumulate", "noahmp_hip_route_runoff", "noahmp_hip_flow_fill_init", "noahmp_hip_flow_fill", "noahmp_hip_flow_basin_init", "noahmp_hip_flow_basin_jump", "noahmp_hip_flow_basin_resolve", "noahmp_hip_flow_upstream_init", "noahmp_hip_flow_upstream_pass", "noahmp_hip_flow_channel", "noahmp_hip_route_kinematic", "noahmp_hip_lake_take", "noahmp_hip_lake_release", "noahmp_hip_scatter_fields", "noahmp_hip_scatter_chunk", "noahmp_hip_scatter_chunk_of", "noahmp_hip_index_width", "noahmp_hip_sorted_exchange", "noahmp_hip_sort_columns", "noahmp_hip_sort_set_band", "noahmp_hip_sort_set_veg_order", "noahmp_hip_sort_staleness", "noahmp_hip_sort_staleness_async", "noahmp_hip_sort_staleness_result", "noahmp_hip_permute_step_arrays", "noahmp_hip_scatter_plan", "noahmp_hip_stream_sync", "noahmp_hip_wtable_mmf", "noahmp_hip_wtable_mmf_async", "noahmp_hip_wtable_lateral_async", "noahmp_hip_wtable_columns_async", "noahmp_hip_groundwater_init", "noahmp_hip_halo_init", "noahmp_hip_exchange_halo", "noahmp_hip_halo_finalize", "noahmp_hip_halo_selftest_rccl", "noahmp_hip_sizeof_wtable_args", "noahmp_hip_malloc", "noahmp_hip_memcpy", "noahmp_hip_free", "noahmp_hip_jit_compile_check", "noahmp_hip_jit_cache_info", "noahmp_hip_jit_source_hash", "noahmp_hip_set_option", "noahmp_hip_debug_live_host_registrations", "noahmp_hip_debug_copy_stats", "noahmp_hip_error_string",
+    "noahmp_hip_step", "noahmp_hip_fetch", "noahmp_hip_step_async", "noahmp_hip_sync", "noahmp_hip_sync_timing", "noahmp_hip_sync_step_timing", "noahmp_hip_sync_counts", "noahmp_hip_fetch_cost", "noahmp_hip_init", "noahmp_hip_forcing_prep", "noahmp_hip_forcing_interpolate", "noahmp_hip_forcing_interpolate_prep", "noahmp_hip_declination", "noahmp_hip_gather_fields", "noahmp_hip_output_fields", "noahmp_hip_history_step", "noahmp_hip_history_finish", "noahmp_hip_region_plan_size", "noahmp_hip_region_plan", "noahmp_hip_region_plan_follow", "noahmp_hip_region_scratch_size", "noahmp_hip_region_step", "noahmp_hip_regrid_plan_size", "noahmp_hip_regrid_plan_latlon", "noahmp_hip_forcing_regrid", "noahmp_hip_forcing_regrid_met", "noahmp_hip_regrid_conserve_plan_size", "noahmp_hip_regrid_conserve_plan", "noahmp_hip_regrid_conserve_scratch_size", "noahmp_hip_forcing_regrid_conserve", "noahmp_hip_forcing_cosz_mean", "noahmp_hip_forcing_shortwave", "noahmp_hip_forcing_shadow", "noahmp_hip_forcing_shortwave_lit", "noahmp_hip_skyview", "noahmp_hip_forcing_radiation_sky", "noahmp_hip_wind_terrain", "noahmp_hip_forcing_wind", "noahmp_hip_flow_terrain", "noahmp_hip_flow_inmask", "noahmp_hip_flow_accumulate", "noahmp_hip_route_runoff", "noahmp_hip_flow_fill_init", "noahmp_hip_flow_fill", "noahmp_hip_flow_basin_init", "noahmp_hip_flow_basin_jump", "noahmp_hip_flow_basin_resolve", "noahmp_hip_flow_upstream_init", "noahmp_hip_flow_upstream_pass", "noahmp_hip_flow_channel", "noahmp_hip_route_kinematic", "noahmp_hip_lake_take", "noahmp_hip_lake_release", "noahmp_hip_flow_drop", "noahmp_hip_route_diffusive", "noahmp_hip_lake_depth", "noahmp_hip_scatter_fields", "noahmp_hip_scatter_chunk", "noahmp_hip_scatter_chunk_of", "noahmp_hip_index_width", "noahmp_hip_sorted_exchange", "noahmp_hip_sort_columns", "noahmp_hip_sort_set_band", "noahmp_hip_sort_set_veg_order", "noahmp_hip_sort_staleness", "noahmp_hip_sort_staleness_async", "noahmp_hip_sort_staleness_result", "noahmp_hip_permute_step_arrays", "noahmp_hip_scatter_plan", "noahmp_hip_stream_sync", "noahmp_hip_wtable_mmf", "noahmp_hip_wtable_mmf_async", "noahmp_hip_wtable_lateral_async", "noahmp_hip_wtable_columns_async", "noahmp_hip_groundwater_init", "noahmp_hip_halo_init", "noahmp_hip_exchange_halo", "noahmp_hip_halo_finalize", "noahmp_hip_halo_selftest_rccl", "noahmp_hip_sizeof_wtable_args", "noahmp_hip_malloc", "noahmp_hip_memcpy", "noahmp_hip_free", "noahmp_hip_jit_compile_check", "noahmp_hip_jit_cache_info", "noahmp_hip_jit_source_hash", "noahmp_hip_set_option", "noahmp_hip_debug_live_host_registrations", "noahmp_hip_debug_copy_stats", "noahmp_hip_error_string",
     "noahmp_hip_last_error", "noahmp_hip_finalize",
 ]
 

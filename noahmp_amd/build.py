@@ -15,7 +15,8 @@ SOURCES = ["noahmp_engine.hip", "noahmp_groundwater.hip", "noahmp_init.hip", "no
            "noahmp_jit.hip", "noahmp_sort.hip", "noahmp_halo.hip", "noahmp_stage.hip", "noahmp_history.hip", "noahmp_regions.hip",
            "noahmp_regrid.hip", "noahmp_shortwave.hip", "noahmp_regrid_conserve.hip", "noahmp_shadow.hip",
            "noahmp_skyview.hip", "noahmp_wind.hip", "noahmp_routing.hip", "noahmp_flow_fill.hip",
-           "noahmp_basins.hip", "noahmp_accum.hip", "noahmp_channel.hip", "noahmp_lakes.hip"]
+           "noahmp_basins.hip", "noahmp_accum.hip", "noahmp_channel.hip", "noahmp_lakes.hip",
+           "noahmp_diffusive.hip"]
 
 
 def _headers():

@@ -125,4 +125,34 @@ NMP_DEV uint32_t lake_release_one(const LakeReleaseArgs& r, int l) {
   return emptied;
 }
 
+struct LakeDepthArgs {
+  const int32_t* member_cell; const int32_t* member_lake;
+  const long long* volume;
+  const double* area; const double* datum;
+  const float* bed;
+  float* depth;
+  long long nmember, ncell;
+  double q;
+  int nlake;
+};
+
+// One entry of noahmp_hip_lake_depth: the lake's surface above the member's bed goes into the depth plane of the diffusive routing call,
+// 0 where the bed stands above the surface.  The pad rule is the take's.
+NMP_DEV void lake_depth_entry(const LakeDepthArgs& t, long long e) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  if (e >= t.nmember) return;
+  const long long c = (long long)t.member_cell[e];
+  const int l = (int)t.member_lake[e];
+  if (c < 0 || c >= t.ncell || l < 0 || l >= t.nlake) return;      // the pad value rule
+  const double area = t.area[l];
+  const double vol = (double)t.volume[l] * t.q;
+  const double hq = vol / area;
+  const double h = (area > 0.0) ? hq : 0.0;
+  const double el = t.datum[l] + h;
+  const double d = el - (double)t.bed[c];
+  t.depth[c] = (d > 0.0) ? (float)d : 0.f;
+}
+
 }  // namespace nmp

@@ -13,6 +13,10 @@
 //                          at most what the lake holds, cut to 24 significant bits so that it is a float32 value, written to
 //                          out_new[outlet].  diag counts the lakes that released all they held: a ballot per wave, one atomic per wave
 //                          that has something to report.
+// noahmp_hip_lake_depth    ONE launch, one thread per entry of the take's member list, after the release: the lake's surface (datum +
+//                          volume * quantum / area, float64) above the member's bed is written to the depth plane the diffusive routing
+//                          call (noahmp_diffusive.hip) reads in its next launch: a channel that drains into the lake sees its stage.
+//                          No LDS, no atomics.
 // Arguments go by value, nothing is allocated, nothing waits on the host.
 #include <math.h>
 #include <string.h>
@@ -94,6 +98,10 @@ __global__ void __launch_bounds__(kBlock) noahmp_lake_release_kernel(const LakeR
   if (!k.diag) return;                                             // the same for every thread of the launch
   const unsigned long long any = __ballot(emptied != 0u);
   if ((threadIdx.x & (kWave - 1)) == 0 && any) atomicAdd(k.diag, (uint32_t)__popcll(any));
+}
+
+__global__ void __launch_bounds__(kBlock) noahmp_lake_depth_kernel(const LakeDepthArgs t) {
+  lake_depth_entry(t, (long long)blockIdx.x * kBlock + threadIdx.x);           // past the list: nothing
 }
 
 // two planes of na and nb bytes that share a byte (or start at the same address, whatever the sizes)
@@ -182,6 +190,36 @@ int noahmp_hip_lake_release(const noahmp_lake_release* r, void* stream) {
   k.r.ncell = (long long)r->ncell; k.r.q = r->quantum; k.r.invq = 1.0 / r->quantum; k.r.dt = r->dt; k.r.nlake = r->nlake;
   k.diag = r->diag;
   hipLaunchKernelGGL(noahmp_lake_release_kernel, grid_1d(r->nlake, kBlock), dim3(kBlock), 0, stream_of(stream), k);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int noahmp_hip_lake_depth(const noahmp_lake_depth* t, void* stream) {
+  const char* me = "noahmp_hip_lake_depth";
+  if (!t) return refuse(-105, "%s: the argument block is NULL", me);
+  if (bad_count(t->nmember)) return refuse(-105, "%s: nmember: 0 .. 2^31 - 1 entries", me);
+  if (t->nlake < 0) return refuse(-105, "%s: nlake must be >= 0", me);
+  if (bad_count(t->ncell)) return refuse(-105, "%s: %s", me, kNcellText);
+  if (t->nmember > 0 && (!t->member_cell || !t->member_lake)) return refuse(-105, "%s: member_cell and member_lake are required where nmember > 0", me);
+  if (t->ncell > 0 && (!t->bed || !t->depth)) return refuse(-105, "%s: bed and depth are required where ncell > 0", me);
+  if (t->nlake > 0 && (!t->volume || !t->area || !t->datum)) return refuse(-105, "%s: volume, area and datum are required where nlake > 0", me);
+  if (bad_quantum(t->quantum)) return refuse(-105, "%s: %s", me, kQuantumText);
+  if (misaligned(t->volume, 8) || misaligned(t->area, 8) || misaligned(t->datum, 8))
+    return refuse(-105, "%s: volume, area and datum hold 8-byte words and must be aligned to 8 bytes", me);
+  if (misaligned(t->bed, 4) || misaligned(t->depth, 4)) return refuse(-105, "%s: bed and depth hold 4-byte words and must be aligned to 4 bytes", me);
+  const uint64_t nm = 4u * (uint64_t)t->nmember, nc = 4u * (uint64_t)t->ncell, n8 = 8u * (uint64_t)t->nlake;
+  if (overlap(t->depth, nc, t->member_cell, nm) || overlap(t->depth, nc, t->member_lake, nm) || overlap(t->depth, nc, t->bed, nc) ||
+      overlap(t->depth, nc, t->volume, n8) || overlap(t->depth, nc, t->area, n8) || overlap(t->depth, nc, t->datum, n8))
+    return refuse(-105, "%s: depth must not share bytes with member_cell, member_lake, bed, volume, area or datum", me);
+  int rc = nmp_host::ensure_init();
+  if (rc) return rc;
+  if (t->nmember == 0 || t->nlake == 0 || t->ncell == 0) return 0;
+  LakeDepthArgs k;
+  memset(&k, 0, sizeof(k));
+  k.member_cell = t->member_cell; k.member_lake = t->member_lake; k.volume = (const long long*)t->volume; k.area = t->area; k.datum = t->datum;
+  k.bed = t->bed; k.depth = t->depth;
+  k.nmember = (long long)t->nmember; k.ncell = (long long)t->ncell; k.nlake = t->nlake; k.q = t->quantum;
+  hipLaunchKernelGGL(noahmp_lake_depth_kernel, grid_1d((long)t->nmember, kBlock), dim3(kBlock), 0, stream_of(stream), k);
   HIPCHK(hipGetLastError());
   return 0;
 }

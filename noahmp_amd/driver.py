@@ -1076,6 +1076,81 @@ class Engine:
         written to out_new at the outlet.  One kernel launch, enqueued only (noahmp_hip_lake_release)."""
         self._call("noahmp_hip_lake_release", C.byref(block), stream)
 
+    @staticmethod
+    def lake_depth_block(member_cell, member_lake, volume, area, datum, bed, depth, quantum):
+        """A noahmp_lake_depth block: the member lists of the take, volume int64 and area, datum float64 device words per lake, bed and
+        depth float32 window planes (depth: the depth_new of the diffusive routing call).  The tensors are kept alive by the block."""
+        import torch
+        nlake = int(volume.numel())
+        assert member_cell.dtype == torch.int32 and member_lake.dtype == torch.int32 and member_cell.numel() == member_lake.numel()
+        assert volume.dtype == torch.int64 and area.dtype == torch.float64 and datum.dtype == torch.float64
+        assert area.numel() == nlake and datum.numel() == nlake
+        assert bed.dtype == torch.float32 and depth.dtype == torch.float32 and bed.numel() == depth.numel()
+        keep = dict(member_cell=member_cell, member_lake=member_lake, volume=volume, area=area, datum=datum, bed=bed, depth=depth)
+        for name, t in keep.items():
+            assert t.is_contiguous(), name
+        b = abi.LakeDepth()
+        _fill(b, keep)
+        b.nmember, b.nlake, b.ncell, b.quantum = int(member_cell.numel()), nlake, int(depth.numel()), float(quantum)
+        return b
+
+    def lake_depth(self, block, stream=None):
+        """After lake_release: every listed member's depth becomes the lake's surface (datum + volume*quantum/area) above the member's
+        bed, 0 where the bed is higher.  One kernel launch, enqueued only (noahmp_hip_lake_depth)."""
+        self._call("noahmp_hip_lake_depth", C.byref(block), stream)
+
+    # ---- diffusive-wave routing on the D8 network: backwater (noahmp_diffusive.hip; helper: noahmp_amd/routing.py DiffusiveFlow)
+    @staticmethod
+    def flow_drop_block(dir, drop, dx, dy, height=None, slope=None):
+        """A noahmp_flow_drop block over the (nj, ni) WINDOW plane dir (uint8, device): drop and exactly one of height and slope are
+        float32 planes of the same shape.  The tensors are kept alive by the returned block."""
+        import torch
+        assert dir.dim() == 2 and dir.is_contiguous() and dir.dtype == torch.uint8
+        keep = dict(height=height, slope=slope, dir=dir, drop=drop)
+        for name, t in keep.items():
+            if t is not None and name != "dir":
+                assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == dir.numel(), name
+        b = abi.FlowDrop()
+        _fill(b, keep)
+        b.nj, b.ni = (int(v) for v in dir.shape)
+        b.dx, b.dy = float(dx), float(dy)
+        return b
+
+    def flow_drop(self, block, stream=None):
+        """The bed drop of every cell of a block of Engine.flow_drop_block to its downstream cell.  One kernel launch, enqueued only,
+        once per terrain (noahmp_hip_flow_drop)."""
+        self._call("noahmp_hip_flow_drop", C.byref(block), stream)
+
+    @staticmethod
+    def route_diffusive_block(inmask, col_index, dir, area, width, length, conv, manning, drop, storage, out_old, out_new, runoff_a, runoff_b,
+                              depth_old, depth_new, scale, dt, limit=0.5, diag=None):
+        """A noahmp_route_diffusive block over the (nj, ni) WINDOW: inmask and dir uint8, col_index int32, the others float32 device
+        planes of the window; runoff_a / runoff_b (or None) in the column order of the store; diag an int32 tensor of four words or
+        None.  The tensors are kept alive by the returned block."""
+        import torch
+        assert inmask.dim() == 2 and inmask.dtype == torch.uint8 and dir.dtype == torch.uint8 and col_index.dtype == torch.int32
+        keep = dict(inmask=inmask, col_index=col_index, dir=dir, area=area, width=width, length=length, conv=conv, manning=manning, drop=drop,
+                    storage=storage, out_old=out_old, out_new=out_new, runoff_a=runoff_a, runoff_b=runoff_b, depth_old=depth_old,
+                    depth_new=depth_new)
+        for name, t in keep.items():
+            if t is not None:
+                assert t.is_contiguous() and (name.startswith("runoff") or t.numel() == inmask.numel()), name
+                assert name in ("inmask", "col_index", "dir") or t.dtype == torch.float32, name
+        if diag is not None:
+            assert diag.dtype == torch.int32 and diag.is_contiguous() and diag.numel() >= 4
+            keep["diag"] = diag
+        b = abi.RouteDiffusive()
+        _fill(b, keep)
+        b.nj, b.ni = (int(v) for v in inmask.shape)
+        b.scale, b.dt, b.limit = float(scale), float(dt), float(limit)
+        return b
+
+    def route_diffusive(self, block, ncol, stream=None):
+        """One diffusive-wave step of a block of Engine.route_diffusive_block: the gather and input of route_kinematic, then Manning's
+        discharge at the slope of the water surface to the downstream cell, nothing where that surface is not lower, at most `limit`
+        times the levelling volume.  One kernel launch, enqueued only (noahmp_hip_route_diffusive)."""
+        self._call("noahmp_hip_route_diffusive", C.byref(block), int(ncol), stream)
+
     def groundwater_init(self, store, stream=None):
         """GROUNDWATER_INIT + EQSMOISTURE (reference drv:1286-1522): equilibrium soil moisture, deep-layer moisture
         and water-table adjustment for OPT_RUN=5, in place.  ide+1 / jde+1 as NOAHMP_INIT receives them (hdrv:291)."""

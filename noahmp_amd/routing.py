@@ -406,9 +406,11 @@ class FlowNetwork:
             self._auto_input(store)                                      # once: the columns the step advances
         return store.a[fields[0]], (store.a[fields[1]] if len(fields) > 1 else None)
 
-    def _sub_steps(self, launch, dt, nsub, comm, geom, stream):
-        """The loop of step() and ChannelFlow.step(): nsub times launch(out_old, out_new), ping-ponging the two out planes, with the
-        exchange of the new plane under THE STREAM RULE of step()."""
+    def _sub_steps(self, launch, dt, nsub, comm, geom, stream, also=None):
+        """The loop of step(), ChannelFlow.step() and DiffusiveFlow.step(): nsub times launch(out_old, out_new), ping-ponging the two
+        out planes, with the exchange of the new plane under THE STREAM RULE of step().  also: None, or a function of the new index
+        that returns further planes written by that launch (DiffusiveFlow: the new depth plane); they travel with out[new] in the same
+        exchange_halo call, so their ring has arrived before the next launch as well."""
         for _ in range(int(nsub)):
             new = 1 - self.cur
             launch(self.out[self.cur], self.out[new])
@@ -417,7 +419,7 @@ class FlowNetwork:
                 f(self.out[new], float(dt) / nsub, comm, stream)
             if comm is not None:
                 self.engine.stream_sync(stream)                          # out[new] is written before it travels
-                comm.exchange_halo([self.out[new]], geom)
+                comm.exchange_halo([self.out[new]] + (list(also(new)) if also is not None else []), geom)
                 self.torch.cuda.current_stream().synchronize()           # ... and its ring has arrived before anybody reads it
         self.last_dt = float(dt) / nsub
 
@@ -1070,6 +1072,111 @@ class ChannelFlow:
         return int(comm.reduce_sum(n)) if comm is not None else n
 
 
+class DiffusiveFlow(ChannelFlow):
+    """Diffusive-wave routing on a FlowNetwork: backwater (noahmp_hip_flow_drop / noahmp_hip_route_diffusive).  Where ChannelFlow
+    releases Manning's discharge at the bed slope, the friction slope here is the slope of the water surface to the downstream cell: a
+    cell whose surface is not above its downstream cell's releases nothing, so water pools behind an adverse bed, crosses flats and
+    filled depressions by its own surface slope, and backs up in front of a lake (Lakes.set_datum).
+
+        df = DiffusiveFlow(net)
+        df.set_geometry(w, 0.05, limit=0.5)                      # once: ChannelFlow's launch, then the bed drops; two depth planes
+        engine.noahmplsm(store, ...); df.step(store, dt, nsub=4) # per step, INSTEAD of net.step / ch.step
+        df.courant(), df.capped(), df.limited(), df.blocked(); df.reset_diag()
+        df.depth(); df.state_dict() / df.load_state_dict()       # the depth plane is read by the next call: restart state
+
+    Choosing nsub: keep courant() near or below 1 as for ChannelFlow; limited() counts the (cell, launch) pairs in which the limiter
+    cut a release -- a few near level pools are the scheme at work, many on a slope say that nsub is too small.
+    df.report = False runs the launches without the diag words: where most workgroups hold a blocked cell their atomics to one word cost
+    more than the launch itself (profiles/diffusive_bench.md); the planes have the same bits either way.
+    Not represented: reverse flow against the fixed directions, dynamic directions, an inertial or implicit formulation, trapezoidal
+    sections, losses; nsub is the caller's choice."""
+
+    def __init__(self, net):
+        super().__init__(net)
+        self.drop = self.bed = None
+        self.limit = 0.5
+        self.report = True                                               # False: the launches get no diag (every workgroup that reports sends atomics)
+        self._d = None                                                   # two depth planes, ping-ponged in step with net.out
+
+    def set_geometry(self, width, manning, smin=1e-4, height=None, slope=None, limit=0.5):
+        """ChannelFlow.set_geometry (length and conv: the outlets release at normal depth), then the bed drop of every cell from the
+        same height or slope plane (one more launch).  With heights (given, or net.filled) the bed is kept as `bed`: Lakes.set_datum
+        needs it.  limit: the flow limiter, finite and > 0."""
+        torch, net = self.torch, self.net
+        if not (math.isfinite(float(limit)) and float(limit) > 0):
+            raise ValueError("limit must be finite and > 0")
+        if slope is None and height is None:
+            height = net.filled
+        super().set_geometry(width, manning, smin=smin, height=height, slope=slope)
+        h = s = None
+        if slope is not None:
+            s = self._cut(slope, "slope")
+        else:
+            h = self._cut(height, "height")
+        dev = net.dir.device
+        self.limit = float(limit)
+        self.bed = h
+        self.drop = torch.empty(net.block_shape, dtype=torch.float32, device=dev)
+        self._d = [torch.zeros(net.block_shape, dtype=torch.float32, device=dev) for _ in range(2)]
+        self._depth = None
+        self.diag = torch.zeros(4, dtype=torch.int32, device=dev)        # the bits of the largest cr; capped, limited, blocked cells
+        torch.cuda.current_stream().synchronize()
+        self.engine.flow_drop(self.engine.flow_drop_block(net.dir, self.drop, net.dx, net.dy, height=h, slope=s))
+        self.engine.stream_sync()
+
+    def step(self, store, dt, fields=("runsfxy", "runsbxy"), nsub=1, comm=None, geom=None, stream=None):
+        """One model step of routing after Engine.noahmplsm, INSTEAD of FlowNetwork.step / ChannelFlow.step: nsub launches with dt/nsub
+        and scale = dt*1e-3/nsub.  The two depth planes ping-pong in step with the network's out planes, and with a comm the new depth
+        plane travels with out in the same exchange: its ring has arrived before the next launch (the stream rule of
+        FlowNetwork.step).  The four diag words accumulate until reset_diag()."""
+        net = self.net
+        if self.drop is None:
+            raise ValueError("call set_geometry() first")
+        ra, rb = net._runoff_planes(store, fields, nsub)
+        scale = float(np.float32(dt) * np.float32(1e-3)) / nsub
+        dts = float(dt) / nsub
+
+        def launch(out_old, out_new):
+            b = self.engine.route_diffusive_block(net.inmask, net.col_index, net.dir, net.area, self.width, self.length, self.conv,
+                                                  self.manning, self.drop, net.storage, out_old, out_new, ra, rb, self._d[net.cur],
+                                                  self._d[1 - net.cur], scale, dts, limit=self.limit, diag=self.diag if self.report else None)
+            self.engine.route_diffusive(b, net.ncell, stream=stream)    # net.cur flips after the launch: _d[net.cur] is then the new plane
+
+        net._sub_steps(launch, dt, nsub, comm, geom, stream, also=lambda new: [self._d[new]])
+
+    def depth(self):
+        """The water depth [m] at the end of the last launch, a plane of the block: what the next launch reads as its neighbours'."""
+        return self._d[self.net.cur]
+
+    def _diag_words(self):
+        self.engine.stream_sync()                                        # the one host wait
+        return tuple(int(v) for v in self.diag.cpu().numpy().view(np.uint32))
+
+    def capped(self, comm=None):
+        """The (cell, launch) pairs since reset_diag() in which a cell released all it held and the limiter did not cut it."""
+        return super().capped(comm)
+
+    def limited(self, comm=None):
+        """The (cell, launch) pairs since reset_diag() in which the limiter cut a release (mod 2^32 per rank; with a comm the sum)."""
+        n = self._diag_words()[2]
+        return int(comm.reduce_sum(n)) if comm is not None else n
+
+    def blocked(self, comm=None):
+        """The (cell, launch) pairs since reset_diag() in which a cell with water released nothing because its surface did not stand
+        above its downstream cell's (mod 2^32 per rank; with a comm the sum)."""
+        n = self._diag_words()[3]
+        return int(comm.reduce_sum(n)) if comm is not None else n
+
+    def state_dict(self):
+        """The restart state: the network's (storage, the current out plane) and the current depth plane (copies)."""
+        return dict(self.net.state_dict(), depth=self.depth().clone())
+
+    def load_state_dict(self, state):
+        self.net.load_state_dict(state)
+        self.depth().copy_(state["depth"])
+        self.torch.cuda.current_stream().synchronize()
+
+
 LAKE_PARAMS = ("area", "weir_h", "weir_c", "weir_l", "orifice_h", "orifice_c", "orifice_a")
 LAKE_WAVE = 64                                                           # every lake's entries are padded to whole waves
 
@@ -1083,6 +1190,7 @@ class Lakes:
         lakes.attach()                                           # after every launch of net.step / ch.step: take, (sum over ranks,) release
         ch.step(store, dt, nsub=2)
         lakes.level(), lakes.outflow(), lakes.volume_m3(), lakes.emptied()
+        lakes.set_datum(Lakes.datum_from_fill(raw, filled, lake_id))     # on a DiffusiveFlow: the lake's stage backs up its inflowing channels
 
     The members of a lake hold everything that reaches them (release and conv are zeroed there, also when set_release, set_velocity or
     set_geometry is called later); after each launch the whole quanta of their storage move to the lake's volume word and the level-pool
@@ -1105,8 +1213,38 @@ class Lakes:
         self.volume = self.inflow = self.params = None
         self._level = self._outflow = self.diag = None
         self._blocks = {}
+        self.datum = None                                                # float64 per lake: the height of level 0 in the bed's datum
+        self._dblocks = {}
 
     # ---- the host helper
+    @staticmethod
+    def datum_from_fill(raw, filled, lake_id):
+        """The datum of every lake of Lakes.from_fill, float64 numpy on the host, on GLOBAL planes: min(filled over the members) -
+        mean(filled - raw over the members).  With it a lake holding area * its mean depth has its surface at the spill level."""
+        raw, filled, lid = np.asarray(raw, np.float64), np.asarray(filled, np.float64), np.asarray(lake_id)
+        assert raw.shape == filled.shape == lid.shape
+        nlake = int(lid.max()) if lid.size else 0
+        m = lid > 0
+        l = lid[m].astype(np.int64) - 1
+        count = np.bincount(l, minlength=nlake).astype(np.float64)
+        spill = np.full(nlake, np.inf)
+        np.minimum.at(spill, l, filled[m])
+        mean = np.bincount(l, weights=(filled - raw)[m], minlength=nlake) / np.maximum(count, 1.0)
+        return np.where(count > 0, spill - mean, 0.0)
+
+    def set_datum(self, datum):
+        """The height of every lake's level 0 [m, in the datum of the bed heights]: a number or nlake values.  With a DiffusiveFlow that
+        has a bed, every launch is then followed by noahmp_hip_lake_depth after the release: the members' depth becomes the lake's
+        surface above their bed, and a channel that drains into the lake backs up until its own surface is higher.  None: off."""
+        self._wait()
+        self._dblocks = {}
+        if datum is None:
+            self.datum = None
+            return
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(datum, np.float64), (self.nlake,)))
+        self.datum = self.torch.from_numpy(d.copy()).to(self.net.dir.device)
+        self.torch.cuda.current_stream().synchronize()
+
     @staticmethod
     def from_fill(raw, filled, upstream_sum, min_depth, min_cells=1, cell_area=1.0):
         """Lakes of a filled terrain, numpy, once per terrain on GLOBAL (nj, ni) planes: the 8-connected components of
@@ -1215,6 +1353,8 @@ class Lakes:
         self._outflow = torch.zeros(nlake, dtype=torch.float32, device=dev)
         self.diag = torch.zeros(1, dtype=torch.int32, device=dev)
         self._blocks = {}
+        self._dblocks = {}
+        self.datum = None
         net.held = torch.from_numpy(held).to(dev)
         net._hold()
         if self.ch is not None and self.ch.conv is not None:
@@ -1241,6 +1381,14 @@ class Lakes:
                 self.inflow.copy_(words)
             self.torch.cuda.current_stream().synchronize()               # ... and the sums have arrived before the release reads them
         self.engine.lake_release(b[1], stream=stream)
+        if self.datum is not None and isinstance(self.ch, DiffusiveFlow) and self.ch.bed is not None:
+            depth = self.ch.depth()                                      # net.cur has flipped: the plane this launch wrote
+            key = (depth.data_ptr(), self.ch.bed.data_ptr())
+            d = self._dblocks.get(key)
+            if d is None:
+                d = self._dblocks[key] = self.engine.lake_depth_block(self.member_cell, self.member_lake, self.volume, self.params["area"],
+                                                                      self.datum, self.ch.bed, depth, self.quantum)
+            self.engine.lake_depth(d, stream=stream)                     # the lake's stage is what the inflowing channels see next
 
     def attach(self):
         """Put the hook into net.after_launch: after every launch of FlowNetwork.step / ChannelFlow.step, before out travels."""
